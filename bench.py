@@ -13,40 +13,49 @@ on every rank over xGMI), domain-pool build, search, winner fit and fp32 fallbac
 rank's shard, its 32-byte (domain, transform, s, o, rms) tuples written by the resolve — at N = 1 straight
 into pinned host memory; at N > 1 (ranks on one host) each rank's resolve writes its shard's tuples into one node-shared pinned host
 buffer, one 4-byte RCCL all-reduce per frame marks it complete (with ranks on several hosts: the RCCL
-all-gather of the tuples + rank 0's D2H) — serial, one frame after another.  Beside it the line carries:
+all-gather of the tuples + rank 0's D2H) — serial, one frame after another.
+
+A plain run sets up, warms up, times the --steps steps, writes the last step's tuples when --dump-outputs
+is given, and prints the line with the headline's own fields (phases_ms, rank_ms_per_step, roofline, arith and
+the records digest all come from the timed steps themselves).  Every other leg and check below runs only
+with --full.  Beside the headline the line carries:
   phases_ms     per phase (frame H2D, frame all-gather, run = prep + search + finish, tuple exchange)
                 the mean over the timed steps, MAX over ranks (phases_ms_by_rank: every rank's)
   rank_ms_per_step  every rank's own step time (ms_per_step / value are the slowest rank's)
-  gather_value  N > 1: the same step with north_star's RCCL all-gather of the tuples + rank 0's D2H in place
+  gather_value  (--full) N > 1: the same step with north_star's RCCL all-gather of the tuples + rank 0's D2H in place
                 of the headline's node-shared host buffer (every rank's resolve writing its shard's tuples
                 into one pinned buffer mapped by all; --tuples gather swaps the two: `node_value`); the
                 records check `gather_equals_headline` verifies the node buffer against it in the same run
-  device_value  the same search with the frame already resident in HBM and the tuples left there
+  device_value  (--full) the same search with the frame already resident in HBM and the tuples left there
                 (the all-gather still runs for N > 1): the device-only rate
-  stream_value  a frame stream: frame k+1's H2D on the context's copy stream overlaps frame k's search
+  stream_value  (--full) a frame stream: frame k+1's H2D on the context's copy stream overlaps frame k's search
                 (one context, two plane buffers; frac_set_frame_async), tuples into pinned memory
-  c5            BASELINE configs[4]: the S1 RGB 4096² frame H2D (N > 1: row stripes + all-gather),
+  c5            (--full) BASELINE configs[4]: the S1 RGB 4096² frame H2D (N > 1: row stripes + all-gather),
                 rgb2yuv on the device, every plane's shard searched, one all-gather of the three
                 planes' tuples, D2H — range-blocks/s over Y + U + V
   roofline      the search kernel against the dense f16 MFMA peak: `achieved` = the matrix flops
                 the search issues per launch (its algorithm's count) ÷ the kernel's mean duration
                 over exactly the headline's timed steps (library HIP events on the kernel's stream,
-                frac_timing_history); `frac_device` the same over the device-resident leg's steps;
+                frac_timing_history); `frac_device` (--full) the same over the device-resident leg's steps;
                 `direct_form` = the §8(d) direct-form op count over the same time (an
                 algorithmic-equivalent rate, not a hardware fraction); `traffic` = HBM bytes per launch
                 from the committed rocprofv3 PMC passes of THIS library build (null when
                 profiles/pmc_search.json was taken from another build)
   arith         what `dtype` "f16" means here: exact integer arithmetic in f16 containers
   records       a digest of the gathered tuples (equal across N = 1/2/4/8 iff the shards' gathered
-                records equal the single-rank run's), and the checks that each rank's slice of the
-                gathered tuples is its own shard and that the legs agree
-  cpu_baseline  the unmodified reference (oracle/_ref) on a bounded sample, all the host cores this
+                records equal the single-rank run's), and with --full the checks that each rank's slice
+                of the gathered tuples is its own shard and that the legs agree
+  alt_engines   (--full, N = 1) the same workload on the VALU and SEA engines, frame resident
+  cpu_baseline  (--full) the unmodified reference (oracle/_ref) on a bounded sample, all the host cores this
                 process may use (affinity, capped by the cgroup CPU quota), CPU model recorded
-  drop_in       (N = 1) the same C3 frame through the reference's own EncodingEngineCore2 with the HIP
+  drop_in       (--full, N = 1) the same C3 frame through the reference's own EncodingEngineCore2 with the HIP
                 engine registered (oracle/ref/core_driver): the rate a reference user gets through
                 its API, alone and beside its CPU engines, and with the batch-claim patch
 
-Run:  python bench.py [--gpus N] [--steps K] [--warmup W] [--engine valu|mfma|auto]
+Run:  python bench.py [--gpus N] [--steps K] [--warmup W] [--engine valu|mfma|auto] [--full] [--dump-outputs DIR]
+--dump-outputs DIR: after the timed steps rank 0 writes the last timed step's gathered tuples, one float64
+array per field in range order (DIR/domain.npy, transform.npy, contrast.npy, brightness.npy, distance.npy);
+the frame is seeded, so two builds run with the same arguments are compared array for array.
 --gpus N > 1 without WORLD_SIZE in the environment: this process launches N ranks itself
 (torch.distributed.run as a child process, before anything touches the GPU) and exits with its
 status; under torch.distributed.run (WORLD_SIZE set) it runs one rank per GPU over RCCL.
@@ -88,6 +97,12 @@ def parse(argv=None):
     ap.add_argument("--engine", default="auto", choices=["auto", "valu", "mfma"])
     ap.add_argument("--size", type=int, default=4096)
     ap.add_argument("--transforms", type=int, default=4)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the other tuple exchange, the device-resident, "
+                         "stream and C5 legs and their checks, the VALU and SEA engines, the CPU baseline and the "
+                         "drop-in runs (the options below size them); off: the headline's timed steps only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's tuples to DIR/<field>.npy (float64, range order; rank 0)")
     ap.add_argument("--cpu-budget", type=float, default=45.0,
                     help="cap in seconds on the CPU-baseline sample (1,024 ranges, ≈28 s at 16 threads; 0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every core this process may use")
@@ -615,6 +630,17 @@ def digest(b: bytes) -> str:
     return hashlib.sha256(b).hexdigest()[:16]
 
 
+def dump_outputs(path: str, tuples: bytes) -> None:
+    """The timed path's result as arrays: the last timed step's gathered 32-byte tuples (what the step leaves in
+    the caller's pinned host memory), one float64 array per field, in range order."""
+    from fractencode_amd import TUPLE
+
+    rec = np.frombuffer(tuples, dtype=TUPLE)
+    os.makedirs(path, exist_ok=True)
+    for name in TUPLE.names:
+        np.save(os.path.join(path, f"{name}.npy"), rec[name].astype(np.float64))
+
+
 def hip_engine(dev, transforms: int, engine_id: int, timing: bool = False):
     """The product engine factory: one fracenc context on `dev` (exhaustive, no classifier, rms 0, sMax −1)."""
     import fractencode_amd as F
@@ -767,8 +793,9 @@ class Bench:
         assert len(hist) == min(args.steps, 256), (len(hist), args.steps)
         self.main_out, st = eng.fetch()  # the timed steps' records (the SEA engine is checked against them)
         self.gathered = step.tuples_bytes()
-        self.own = eng.fetch_tuples().tobytes() if len(self.mine) else b""
-        self.checks["own_slice_in_gather"] = step.own_slice_ok(self.own)
+        if args.full:
+            self.own = eng.fetch_tuples().tobytes() if len(self.mine) else b""
+            self.checks["own_slice_in_gather"] = step.own_slice_ok(self.own)
         phases = clock.means()
         phases.update({k: float(np.mean(hist["ms_" + k])) if len(hist) else 0.0 for k in ("prep", "search", "finish")})
         keys = list(PHASES) + ["prep", "search", "finish"]
@@ -1016,22 +1043,13 @@ class Bench:
     def run(self) -> dict:
         import torch.distributed as dist
 
-        args, world, rank = self.args, self.world, self.rank
+        args, rank = self.args, self.rank
         self.headline()
-        if self.side_steps > 0:
-            if self.ranked:
-                self.other_tuples_leg()
-            self.device_leg()
-            self.stream_leg()
-            self.c5_leg()
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, self.gathered)
+        if args.full:
+            self.full_legs()
         self.line["records"] = {"tuples_sha16": digest(self.gathered), "n": self.nr_total, **self.checks}
-        if world == 1 and self.engine_name == "mfma" and args.alt_steps > 0 and self.product:
-            self.alt_engines()
-        if rank == 0 and world == 1 and args.cpu_budget > 0:
-            threads, host = host_cores()
-            self.line["cpu_baseline"] = cpu_baseline(self.frame, args.cpu_budget, args.cpu_threads or threads, host)
-        if rank == 0 and world == 1 and self.cuda and self.product and args.drop_in:
-            self.line["drop_in"] = drop_in(self.frame)
         self.eng.close()
         if rank == 0:
             print(json.dumps(self.line), flush=True)
@@ -1042,6 +1060,23 @@ class Bench:
             dist.barrier()
             dist.destroy_process_group()
         return self.line
+
+    def full_legs(self) -> None:
+        """--full: everything the line carries beside the headline's own fields."""
+        args, world, rank = self.args, self.world, self.rank
+        if self.side_steps > 0:
+            if self.ranked:
+                self.other_tuples_leg()
+            self.device_leg()
+            self.stream_leg()
+            self.c5_leg()
+        if world == 1 and self.engine_name == "mfma" and args.alt_steps > 0 and self.product:
+            self.alt_engines()
+        if rank == 0 and world == 1 and args.cpu_budget > 0:
+            threads, host = host_cores()
+            self.line["cpu_baseline"] = cpu_baseline(self.frame, args.cpu_budget, args.cpu_threads or threads, host)
+        if rank == 0 and world == 1 and self.cuda and self.product and args.drop_in:
+            self.line["drop_in"] = drop_in(self.frame)
 
 
 def main(args, engine_factory=None, backend: str | None = None, cuda: bool = True) -> dict:

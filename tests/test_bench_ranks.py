@@ -24,7 +24,7 @@ def _run(tmp_path, world, tuples="gather", fail_rank=None, group=False):
     import bench
 
     out = str(tmp_path / f"line_{world}_{tuples}{'_group' if group else ''}.json")
-    argv = ["--gpus", str(world), "--size", str(SIZE), "--steps", str(STEPS), "--warmup", "1", "--side-steps", "1",
+    argv = ["--full", "--gpus", str(world), "--size", str(SIZE), "--steps", str(STEPS), "--warmup", "1", "--side-steps", "1",
             "--cpu-budget", "0", "--tuples", tuples, "--out", out] + (["--group"] if group else [])
     env = dict(os.environ, OMP_NUM_THREADS="1")
     if fail_rank is not None:
@@ -71,6 +71,35 @@ def test_single_rank_line_is_the_oracles(single, oracle):
     assert single["c5"]["records"]["n"] == SIZE * SIZE // 64 + 2 * (SIZE // 2) ** 2 // 64
     for k in ("device_value", "stream_value"):
         assert single[k]["value"] > 0
+
+
+def test_plain_run_times_only_the_headline_and_dumps_its_tuples(tmp_path, single):
+    """Without --full the line has the headline's fields and the records digest but no side leg, baseline or
+    check; --steps sets the number of timed steps; --dump-outputs writes the last timed step's tuples, one
+    float64 array per field in range order, equal to the --full run's records."""
+    import bench
+    import fractencode_amd as F
+
+    out, dump = str(tmp_path / "plain.json"), tmp_path / "dump"
+    argv = ["--gpus", "1", "--size", str(SIZE), "--steps", "3", "--warmup", "1", "--out", out, "--dump-outputs",
+            str(dump)]
+    assert subprocess.call([sys.executable, SCRIPT, *argv], env=dict(os.environ, OMP_NUM_THREADS="1")) == 0
+    line = json.load(open(out))
+    for k in ("device_value", "stream_value", "c5", "alt_engines", "cpu_baseline", "drop_in", "gather_value",
+              "node_value"):
+        assert k not in line, k
+    assert line["steps"] == 3 and len(line["roofline"]["kernel_ms_timed_steps"]) == 3
+    assert line["metric"] == bench.METRIC and line["unit"] == "range-blocks/s" and line["higher_is_better"] is True
+    n = SIZE * SIZE // 64
+    assert abs(line["value"] - n / (line["ms_per_step"] * 1e-3)) <= 1e-3 * line["value"] + 0.1
+    assert line["records"] == {"tuples_sha16": single["records"]["tuples_sha16"], "n": n}
+    assert sorted(p.name for p in dump.iterdir()) == sorted(f"{f}.npy" for f in F.TUPLE.names)
+    rec = np.zeros(n, dtype=F.TUPLE)
+    for f in F.TUPLE.names:
+        a = np.load(dump / f"{f}.npy")
+        assert a.dtype == np.float64 and a.shape == (n,)
+        rec[f] = a
+    assert bench.digest(rec.tobytes()) == line["records"]["tuples_sha16"]
 
 
 @pytest.mark.parametrize("world,tuples", [(2, "gather"), (3, "gather"), (8, "gather"), (2, "node"), (3, "node"),

@@ -15,7 +15,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--size", "512", "--steps", "2", "--warmup", "1", "--side-steps", "1", "--cpu-budget", "0", "--alt-steps",
+ARGS = ["--full", "--size", "512", "--steps", "2", "--warmup", "1", "--side-steps", "1", "--cpu-budget", "0", "--alt-steps",
         "0", "--drop-in", "0"]
 
 
