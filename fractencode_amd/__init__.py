@@ -98,6 +98,15 @@ class FracQuadtreeParams(C.Structure):
     _fields_ = [("max_size", C.c_uint32), ("min_size", C.c_uint32), ("split_distance", C.c_double)]
 
 
+class FracFrc1Info(C.Structure):
+    """struct frac_frc1_info: an FRC1 header's fields, plus record_bits and body_bytes."""
+    _fields_ = [(k, C.c_uint32) for k in ("width", "height", "range_size", "domain_size", "domain_stride",
+                                         "transforms", "contrast_bits", "brightness_bits", "index_bits",
+                                         "record_bits", "n_ranges", "n_domains", "flags")] + \
+               [("body_bytes", C.c_uint64)] + \
+               [(k, C.c_double) for k in ("contrast_min", "contrast_max", "brightness_min", "brightness_max")]
+
+
 class FracError(RuntimeError):
     pass
 
@@ -190,6 +199,9 @@ def lib() -> C.CDLL:
             "frac_copy_tuples_device": (i32, [vp, vp]),
             "frac_set_tuple_sink": (i32, [vp, vp]),
             "frac_pack_frc1": (i32, [vp, u32, u32, vp, sz, C.POINTER(C.c_size_t)]),
+            "frac_frc1_info": (i32, [vp, sz, C.POINTER(FracFrc1Info)]),
+            "frac_decode_frc1": (i32, [vp, vp, sz, u32, i32, C.c_double, vp, sz, C.POINTER(C.c_int),
+                                       C.POINTER(C.c_double)]),
             "frac_fetch_tuples": (i32, [vp, vp]),
             "frac_decode": (i32, [vp, vp, sz, u32, u32, i32, C.c_double, vp, C.POINTER(C.c_int),
                                   C.POINTER(C.c_double)]),
@@ -258,6 +270,17 @@ def preclassify(plane: np.ndarray, items: np.ndarray) -> np.ndarray:
     if rc != 0:
         raise FracError(last_error())
     return items
+
+
+def frc1_info(stream) -> dict:
+    """An FRC1 stream's header, validated against the stream's length on the host (frac_frc1_info): the
+    keys of codec.read_header without magic and version, plus record_bits and body_bytes.  Raises
+    FracError on a stream frac_decode_frc1 would refuse by its header."""
+    buf = np.frombuffer(stream, dtype=np.uint8)
+    out = FracFrc1Info()
+    if lib().frac_frc1_info(buf.ctypes.data if len(buf) else None, len(buf), C.byref(out)) != 0:
+        raise FracError(last_error())
+    return {k: getattr(out, k) for k, _ in FracFrc1Info._fields_}
 
 
 def transform_index(n: int, t: int, pix: int) -> int:
@@ -477,6 +500,24 @@ class Engine:
                                           height, max_iter, rms_eps, plane.ctypes.data, C.byref(it), C.byref(rms)))
         return plane, it.value, rms.value
 
+    def decode_frc1(self, stream, scale: int = 1, max_iter: int = -1, rms_eps: float = 1e-5,
+                    initial: np.ndarray | None = None):
+        """Decoder2::decode of an FRC1 stream on the GPU (frac_decode_frc1): unpacked, validated and decoded
+        on the device, every coordinate and size multiplied by `scale` (1..16).  `initial` as in decode(),
+        sized scale·H × scale·W.  Returns (plane, iterations, rms)."""
+        h = frc1_info(stream)
+        k = scale if 1 <= scale <= 16 else 0  # the library refuses the scale; no plane is sized by it
+        W, H = k * h["width"], k * h["height"]
+        plane = np.zeros((H, W), np.uint8) if initial is None else np.ascontiguousarray(initial, np.uint8).copy()
+        if plane.shape != (H, W):
+            raise FracError(f"decode_frc1: initial must be {H}x{W}")
+        buf = np.frombuffer(stream, dtype=np.uint8)
+        it = C.c_int()
+        rms = C.c_double()
+        self._check(lib().frac_decode_frc1(self._ctx, buf.ctypes.data, len(buf), scale, max_iter, rms_eps,
+                                           plane.ctypes.data, plane.size, C.byref(it), C.byref(rms)))
+        return plane, it.value, rms.value
+
     def encode_quadtree(self, max_size: int = 16, min_size: int = 4, split_distance: float = 10.0, out=None,
                         allow_short: bool = False, leaves: bool = False):
         """Quadtree partition of the frame set on this engine (frac_encode_quadtree): ranges of
@@ -575,3 +616,10 @@ def encode(plane: np.ndarray, range_size: int = 4, domain_size: int = 16, transf
         e.set_frame(plane)
         e.set_domains(doms)
         return e.search(rngs)
+
+
+def decode_stream(stream, scale: int = 1, device: int = 0, **kw):
+    """One call from an FRC1 stream to pixels, beside encode(): Engine.decode_frc1 on a context of its own
+    (kw: max_iter, rms_eps, initial).  Returns (plane, iterations, rms)."""
+    with Engine(device) as e:
+        return e.decode_frc1(stream, scale, **kw)

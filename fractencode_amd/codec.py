@@ -30,6 +30,7 @@ had no eligible domain (the reference's default record, encode/datatypes.h:8-26)
 When every value of a field is equal the quantizer would be degenerate (the reference
 asserts max > min, Quantizer.hpp:19): the header then stores min == max and every
 record dequantizes to exactly that value.
+frac_decode_frc1 (Engine.decode_frc1) consumes this layout on the device; unpack_stream is its host restatement.
 """
 from __future__ import annotations
 

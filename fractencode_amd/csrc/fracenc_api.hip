@@ -24,6 +24,7 @@
 #include "fracenc_classify.hip"
 #include "fracenc_sea.hip"
 #include "fracenc_stream.hip"
+#include "fracenc_frc1dec.hip"
 #include "fracenc_tp.hip"
 #include "fracenc_gen.hip"
 #include "fracenc_bucket.hip"
@@ -271,6 +272,7 @@ struct frac_ctx {
     DBuf<Frc1MinMax> d_frc_mm;             // frac_pack_frc1
     DBuf<unsigned long long> d_frc_rec;
     DBuf<uint32_t> d_frc_words;
+    DBuf<uint32_t> d_frc_in, d_frc_status; // frac_decode_frc1: the padded stream body; {bad, domain-less} counts
     std::vector<frac_encode_item> qt_res; // quadtree: one level's results (kept: no page faults per call)
     // quadtree: the per-level domain grids (geometry only) of the last frame size, by log2(n)
     uint32_t qt_w = 0, qt_h = 0;
@@ -2926,6 +2928,8 @@ void frac_destroy(frac_ctx* c)
     c->d_frc_mm.release();
     c->d_frc_rec.release();
     c->d_frc_words.release();
+    c->d_frc_in.release();
+    c->d_frc_status.release();
     c->d_sea_ent.release();
     c->d_sea_tmp.release();
     c->d_m_entries.release();
@@ -3714,15 +3718,18 @@ static bool covers_exactly(const std::vector<frac_grid_item>& rects, uint32_t w,
     return covered == cell.size();
 }
 
-// Fused decode (fracenc_decode.hip decode_fused / decode_check): the items tile the plane.
-static int decode_fused_impl(frac_ctx* c, const frac_encode_item* d_items, size_t n, uint32_t w, uint32_t h,
-                             int iters, double eps, uint8_t* plane, int* iterations, double* rms)
+// The fused decoders' loop: `step(src, tgt, stride)` enqueues one iteration that writes every pixel of tgt
+// from src and adds its (source − new)² sums to the kDecodeSlots slots (decode_fused over items, frc1dec_step
+// over a stream's records); decode_check, the buffer swap and the host's look at the flag every few steps
+// are shared.
+extern "C++" template <class Step>
+static int decode_fused_loop(frac_ctx* c, uint32_t w, uint32_t h, int iters, double eps, uint8_t* plane,
+                             int* iterations, double* rms, Step&& step)
 {
     const uint32_t stride = (w + 63u) & ~63u;
     const size_t bytes = (size_t)stride * (h + 1);
     FRAC_HIP(c, c->d_dec_src.ensure(bytes));
     FRAC_HIP(c, c->d_dec_tgt.ensure(bytes));
-    const uint32_t nblk = (uint32_t)((n + 3) / 4);
     FRAC_HIP(c, c->d_dec_part.ensure(kDecodeSlots));
     FRAC_HIP(c, hipMemsetAsync(c->d_dec_part.ptr, 0, kDecodeSlots * sizeof(unsigned long long), c->stream));
     FRAC_HIP(c, c->d_dec_state.ensure(1));
@@ -3733,18 +3740,12 @@ static int decode_fused_impl(frac_ctx* c, const frac_encode_item* d_items, size_
     FRAC_HIP(c, hipMemsetAsync(buf[1], 0, bytes, c->stream));
     FRAC_HIP(c, hipMemcpy2DAsync(buf[1], stride, plane, w, w, h, hipMemcpyHostToDevice, c->stream));
     FRAC_HIP(c, hipMemsetAsync(c->d_dec_state.ptr, 0, sizeof(DecodeState), c->stream));
-    DecodeArgs a;
-    a.stride = stride;
-    a.items = d_items;
-    a.n = (uint32_t)n;
     constexpr int kChunk = 8; // iterations enqueued between host checks of the convergence flag
     int enq = 0;
     while (enq < iters) {
         const int stop = std::min(iters, enq + kChunk);
         for (; enq < stop; ++enq) {
-            a.src = buf[enq & 1];
-            a.tgt = buf[(enq + 1) & 1];
-            decode_fused<<<nblk, 256, 0, c->stream>>>(a, c->d_dec_state.ptr, c->d_dec_part.ptr);
+            step(buf[enq & 1], buf[(enq + 1) & 1], stride);
             decode_check<<<1, kDecodeSlots, 0, c->stream>>>(c->d_dec_part.ptr, (uint64_t)w * h, eps, enq, iters - 1,
                                                             c->d_dec_state.ptr);
         }
@@ -3771,6 +3772,23 @@ static int decode_fused_impl(frac_ctx* c, const frac_encode_item* d_items, size_
     if (rms)
         *rms = r;
     return FRAC_OK;
+}
+
+// Fused decode (fracenc_decode.hip decode_fused / decode_check): the items tile the plane.
+static int decode_fused_impl(frac_ctx* c, const frac_encode_item* d_items, size_t n, uint32_t w, uint32_t h,
+                             int iters, double eps, uint8_t* plane, int* iterations, double* rms)
+{
+    DecodeArgs a;
+    a.items = d_items;
+    a.n = (uint32_t)n;
+    const uint32_t nblk = (uint32_t)((n + 3) / 4);
+    return decode_fused_loop(c, w, h, iters, eps, plane, iterations, rms,
+                             [&](const uint8_t* src, uint8_t* tgt, uint32_t stride) {
+                                 a.src = src;
+                                 a.tgt = tgt;
+                                 a.stride = stride;
+                                 decode_fused<<<nblk, 256, 0, c->stream>>>(a, c->d_dec_state.ptr, c->d_dec_part.ptr);
+                             });
 }
 
 static int decode_impl(frac_ctx* c, const frac_encode_item* d_items, size_t n, uint32_t w, uint32_t h, int max_iter,
@@ -4018,6 +4036,162 @@ int frac_pack_frc1(frac_ctx* c, uint32_t cbits, uint32_t bbits, uint8_t* out, si
     if (cap > FRAC_FRC1_HEADER_BYTES)
         std::memcpy(out + FRAC_FRC1_HEADER_BYTES, words.data(), std::min<size_t>(cap, total) - FRAC_FRC1_HEADER_BYTES);
     return FRAC_OK;
+}
+
+// The FRC1 header "<4sHHIIIIIBBBBIIdddd" (fractencode_amd/codec.py) parsed and checked against the stream
+// length; on failure `msg` names the rule.
+using Frc1Info = struct frac_frc1_info; // the plain name is the function's
+static int frc1_parse(const uint8_t* s, size_t len, Frc1Info* o, std::string& msg)
+{
+    auto bad = [&](const char* why) {
+        msg = std::string("FRC1: ") + why;
+        return FRAC_E_INVALID;
+    };
+    if (!s || !o)
+        return bad("NULL argument");
+    if (len < FRAC_FRC1_HEADER_BYTES)
+        return bad("truncated header");
+    uint16_t version, flags;
+    uint32_t u[5], counts[2];
+    double mm[4];
+    std::memcpy(&version, s + 4, 2);
+    std::memcpy(&flags, s + 6, 2);
+    std::memcpy(u, s + 8, sizeof(u));
+    std::memcpy(counts, s + 32, sizeof(counts));
+    std::memcpy(mm, s + 40, sizeof(mm));
+    if (std::memcmp(s, "FRC1", 4) != 0 || version != 1)
+        return bad("bad magic or version");
+    *o = Frc1Info{};
+    o->width = u[0], o->height = u[1], o->range_size = u[2], o->domain_size = u[3], o->domain_stride = u[4];
+    o->transforms = s[28], o->contrast_bits = s[29], o->brightness_bits = s[30], o->index_bits = s[31];
+    o->n_ranges = counts[0], o->n_domains = counts[1], o->flags = flags;
+    o->contrast_min = mm[0], o->contrast_max = mm[1], o->brightness_min = mm[2], o->brightness_max = mm[3];
+    if (o->width == 0 || o->height == 0 || o->range_size == 0)
+        return bad("zero width, height or range size");
+    if (o->domain_size < 2 || (o->domain_size & 1u) || o->domain_stride != o->domain_size / 2)
+        return bad("domain size must be even and at least 2, its stride half of it");
+    if (o->transforms < 1 || o->transforms > 8)
+        return bad("transforms outside 1..8");
+    if (o->contrast_bits < 2 || o->contrast_bits > 24 || o->brightness_bits < 2 || o->brightness_bits > 24)
+        return bad("contrast / brightness bits outside [2, 24]");
+    auto bitlen = [](uint64_t v) { uint32_t b = 0; while (v) { ++b; v >>= 1; } return b; };
+    if (o->index_bits != std::max(1u, bitlen(o->n_domains)))
+        return bad("index bits do not match the domain count");
+    o->record_bits = o->index_bits + std::max(1u, bitlen(o->transforms - 1)) + o->contrast_bits + o->brightness_bits;
+    if (o->record_bits > 64)
+        return bad("record wider than 64 bits");
+    if (o->n_ranges != frac_uniform_grid(o->width, o->height, o->range_size, o->range_size, nullptr, 0))
+        return bad("range count is not the range grid's");
+    if (o->n_domains != frac_uniform_grid(o->width, o->height, o->domain_size, o->domain_stride, nullptr, 0))
+        return bad("domain count is not the domain grid's");
+    o->body_bytes = ((uint64_t)o->n_ranges * o->record_bits + 7) / 8;
+    if (len - FRAC_FRC1_HEADER_BYTES < o->body_bytes)
+        return bad("truncated records");
+    for (double v : mm)
+        if (!std::isfinite(v))
+            return bad("non-finite quantizer bound");
+    return FRAC_OK;
+}
+
+int frac_frc1_info(const uint8_t* stream, size_t len, struct frac_frc1_info* out)
+{
+    std::string msg;
+    const int rc = frc1_parse(stream, len, out, msg);
+    if (rc != FRAC_OK)
+        g_last_error = msg;
+    return rc;
+}
+
+int frac_decode_frc1(frac_ctx* c, const uint8_t* stream, size_t len, uint32_t scale, int max_iter, double rms_eps,
+                     uint8_t* plane, size_t plane_bytes, int* iterations, double* rms)
+{
+    if (!c)
+        return FRAC_E_INVALID;
+    Frc1Info h;
+    {
+        std::string msg;
+        if (frc1_parse(stream, len, &h, msg) != FRAC_OK)
+            return c->fail(FRAC_E_INVALID, msg);
+        if (check_ab_knobs(msg) != FRAC_OK)
+            return c->fail(FRAC_E_INVALID, msg);
+    }
+    if (scale < 1 || scale > 16 || (uint64_t)scale * h.width > 65535 || (uint64_t)scale * h.height > 65535)
+        return c->fail(FRAC_E_INVALID, "decode_frc1: scale must be in 1..16 and the scaled frame at most 65535 a side");
+    const uint32_t W = scale * h.width, H = scale * h.height;
+    if (!plane || plane_bytes < (uint64_t)W * H)
+        return c->fail(FRAC_E_INVALID, "decode_frc1: the plane is smaller than the scaled frame");
+    const uint32_t n = h.n_ranges;
+    Frc1Layout L{};
+    L.n_ranges = n;
+    L.n_domains = h.n_domains;
+    L.rcols = n ? (h.width - h.range_size) / h.range_size + 1 : 0;
+    L.dcols = h.n_domains ? (h.width - h.domain_size) / h.domain_stride + 1 : 0;
+    L.range_size = h.range_size;
+    L.domain_size = h.domain_size;
+    L.domain_stride = h.domain_stride;
+    L.index_bits = h.index_bits;
+    L.c_bits = h.contrast_bits;
+    L.b_bits = h.brightness_bits;
+    L.t_bits = h.record_bits - h.index_bits - h.contrast_bits - h.brightness_bits;
+    L.record_bits = h.record_bits;
+    // Quantizer (encode/Quantizer.hpp:19-22): step = |max − min| / 2^bits; !(max > min): every code is min
+    auto step = [](double lo, double hi, uint32_t bits) {
+        return hi > lo ? std::fabs(hi - lo) / (double)(1u << bits) : 0.0;
+    };
+    L.c_step = step(h.contrast_min, h.contrast_max, h.contrast_bits);
+    L.c_min = h.contrast_min;
+    L.b_step = step(h.brightness_min, h.brightness_max, h.brightness_bits);
+    L.b_min = h.brightness_min;
+
+    FRAC_HIP(c, hipSetDevice(c->device));
+    // record pass: reads only the stream buffer (the body and kFrc1PadWords zeroed dwords after it)
+    uint32_t status[2] = {0, 0};
+    if (n) {
+        const size_t body_words = (size_t)((h.body_bytes + 3) / 4);
+        FRAC_HIP(c, c->d_frc_in.ensure(body_words + kFrc1PadWords));
+        FRAC_HIP(c, c->d_frc_rec.ensure(n));
+        FRAC_HIP(c, c->d_frc_status.ensure(2));
+        // from the body's last whole dword on: its tail bytes and the padding
+        FRAC_HIP(c, hipMemsetAsync(c->d_frc_in.ptr + (body_words - 1), 0, (1 + kFrc1PadWords) * sizeof(uint32_t),
+                                   c->stream));
+        FRAC_HIP(c, hipMemsetAsync(c->d_frc_status.ptr, 0, sizeof(status), c->stream));
+        FRAC_HIP(c, hipMemcpyAsync(c->d_frc_in.ptr, stream + FRAC_FRC1_HEADER_BYTES, (size_t)h.body_bytes,
+                                   hipMemcpyHostToDevice, c->stream));
+        frc1dec_records<<<(n + 255) / 256, 256, 0, c->stream>>>(c->d_frc_in.ptr, L, c->d_frc_rec.ptr,
+                                                                 c->d_frc_status.ptr);
+        FRAC_HIP(c, hipGetLastError());
+        FRAC_HIP(c, hipMemcpyAsync(status, c->d_frc_status.ptr, sizeof(status), hipMemcpyDeviceToHost, c->stream));
+        FRAC_HIP(c, hipStreamSynchronize(c->stream));
+        if (status[0])
+            return c->fail(FRAC_E_INVALID, "FRC1: domain index out of range");
+    }
+    const bool tiles = n && h.width % h.range_size == 0 && h.height % h.range_size == 0 && status[1] == 0;
+    if (tiles && h.domain_size == 2 * h.range_size && !(c->p.flags & FRAC_FLAG_DECODE_STEPWISE)) {
+        Frc1StepArgs a;
+        a.w = W;
+        a.h = H;
+        a.R = scale * h.range_size;
+        a.rrows = h.height / h.range_size;
+        a.scale = scale;
+        a.rec = c->d_frc_rec.ptr;
+        const dim3 grid((W + kFrc1TileW - 1) / kFrc1TileW, (H + kFrc1TileH - 1) / kFrc1TileH);
+        return decode_fused_loop(c, W, H, max_iter < 0 ? 300 : max_iter, rms_eps, plane, iterations, rms,
+                                 [&](const uint8_t* src, uint8_t* tgt, uint32_t stride) {
+                                     a.src = src;
+                                     a.tgt = tgt;
+                                     a.stride = stride;
+                                     frc1dec_step<<<grid, 256, 0, c->stream>>>(a, L, c->d_dec_state.ptr,
+                                                                               c->d_dec_part.ptr);
+                                 });
+    }
+    // every other stream: the records as scaled encode items, through the item decoder (fused when they
+    // tile the plane and every range has a domain, as frac_decode decides)
+    FRAC_HIP(c, c->d_dec_items.ensure(n));
+    if (n) {
+        frc1dec_expand<<<(n + 255) / 256, 256, 0, c->stream>>>(c->d_frc_rec.ptr, L, scale, c->d_dec_items.ptr);
+        FRAC_HIP(c, hipGetLastError());
+    }
+    return decode_impl(c, c->d_dec_items.ptr, n, W, H, max_iter, rms_eps, plane, iterations, rms, tiles);
 }
 
 int frac_fetch_tuples(frac_ctx* c, frac_tuple* out)

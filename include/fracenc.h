@@ -306,6 +306,36 @@ int frac_rgb_to_yuv(frac_ctx* ctx, const uint8_t* rgb, uint32_t w, uint32_t h, u
 int frac_pack_frc1(frac_ctx* ctx, uint32_t contrast_bits, uint32_t brightness_bits, uint8_t* out, size_t cap,
                    size_t* n_out);
 
+/* ---- FRC1 streams decoded on the device, at any integer scale ---------------
+ * These two symbols were added after ABI 9 without changing FRAC_ABI_VERSION: probe for them by
+ * name (dlsym) when the library may be older.
+ *
+ * The header's fields plus what follows from them.  The type is named by its struct tag (the
+ * function below has the same name, which C keeps apart from tags and C++ resolves to the function). */
+struct frac_frc1_info {
+    uint32_t width, height, range_size, domain_size, domain_stride;
+    uint32_t transforms, contrast_bits, brightness_bits, index_bits, record_bits;
+    uint32_t n_ranges, n_domains, flags;
+    uint64_t body_bytes;                 /* ceil(n_ranges * record_bits / 8) */
+    double contrast_min, contrast_max, brightness_min, brightness_max;
+};
+/* Host only, no device and no ctx: parse and validate an FRC1 header against the stream length
+ * (message via frac_last_error(NULL)).  FRAC_E_INVALID for: len < 72, wrong magic or version; a zero
+ * width, height or range size; domain_size < 2 or odd, domain_stride != domain_size / 2; transforms
+ * outside 1..8; contrast_bits or brightness_bits outside [2, 24]; index_bits != max(1, bitlen(n_domains));
+ * record_bits > 64; n_ranges / n_domains other than frac_uniform_grid's counts for (range_size,
+ * range_size) / (domain_size, domain_stride); len < 72 + body_bytes; a non-finite min or max.  Trailing
+ * bytes are ignored. */
+int frac_frc1_info(const uint8_t* stream, size_t len, struct frac_frc1_info* out);
+/* Decoder2::decode of the stream's records with every coordinate and size multiplied by `scale`
+ * (1..16, scale·W and scale·H at most 65535): the result of frac_decode on the stream's dequantized
+ * records (Quantizer::value, a degenerate field dequantizes to its min) so scaled.
+ * plane: (scale·W) × (scale·H), row stride scale·W, in/out exactly as frac_decode's plane; plane_bytes
+ * is its capacity.  A record whose index equals n_domains has no domain and its range is left
+ * untouched; an index above n_domains fails the call (FRAC_E_INVALID) before any plane is touched. */
+int frac_decode_frc1(frac_ctx* ctx, const uint8_t* stream, size_t len, uint32_t scale, int max_iter,
+                     double rms_eps, uint8_t* plane, size_t plane_bytes, int* iterations, double* rms);
+
 /* ---- host helpers (no device needed) ------------------------------------ */
 /* createUniformGrid (image/partition2.hpp:109-135): returns the item count and
  * writes min(count, cap) items (categories -1).  Returns 0 where the reference's loop has no

@@ -12,7 +12,7 @@
 //                       thread-dependent, :165-168)
 //   Quantizer<T>        Frac::Quantizer (encode/Quantizer.hpp:7-45) as the built reference
 //                       computes it (value() with the FMA the compiler contracts)
-//   createUniformGrid / preclassify / encodeQuadtree / decode   — the C ABI entry points
+//   createUniformGrid / preclassify / encodeQuadtree / decode / decode_frc1 / frc1_info — the C ABI entry points
 //   Engine's ABI 8/9 methods: an external HIP stream (void*), the tuple sink and 32-byte tuples,
 //                       frame streaming (setFrameAsync / setFrameDeviceAsync), 32-byte quadtree
 //                       leaves, per-run device times
@@ -76,6 +76,17 @@ inline void preclassify(const uint8_t* plane, uint32_t w, uint32_t h, uint32_t s
 {
     if (frac_classify(plane, w, h, stride, items.data(), items.size()) != FRAC_OK)
         throw Error(frac_last_error(nullptr));
+}
+
+// An FRC1 stream's header, parsed and validated against the stream length on the host (frac_frc1_info;
+// the C name is also the function's, hence the alias).
+using Frc1Info = struct ::frac_frc1_info;
+inline Frc1Info frc1_info(const uint8_t* stream, size_t len)
+{
+    Frc1Info info{};
+    if (frac_frc1_info(stream, len, &info) != FRAC_OK)
+        throw Error(std::string("fracenc: ") + frac_last_error(nullptr));
+    return info;
 }
 
 class Engine {
@@ -194,6 +205,27 @@ public:
         double rms = 0.0;
         check(frac_decode(ctx_, items.data(), items.size(), w, h, max_iter, rms_eps, plane.data(), &it, &rms));
         return {it, rms};
+    }
+    // The same for an FRC1 stream (frac_decode_frc1), unpacked and decoded on the device with every
+    // coordinate and size multiplied by `scale`; plane becomes scale·W × scale·H (kept when it already
+    // has that size: the caller's initial target, else zero-filled).
+    std::pair<int, double> decode_frc1(const uint8_t* stream, size_t len, std::vector<uint8_t>& plane,
+                                       uint32_t scale = 1, int max_iter = -1, double rms_eps = 1e-5)
+    {
+        const Frc1Info info = frc1_info(stream, len);
+        const uint32_t k = scale >= 1 && scale <= 16 ? scale : 0; // the library refuses the scale itself
+        const size_t need = (size_t)k * info.width * k * info.height;
+        if (plane.size() != need)
+            plane.assign(need, 0);
+        int it = 0;
+        double rms = 0.0;
+        check(frac_decode_frc1(ctx_, stream, len, scale, max_iter, rms_eps, plane.data(), plane.size(), &it, &rms));
+        return {it, rms};
+    }
+    std::pair<int, double> decode_frc1(const std::vector<uint8_t>& stream, std::vector<uint8_t>& plane,
+                                       uint32_t scale = 1, int max_iter = -1, double rms_eps = 1e-5)
+    {
+        return decode_frc1(stream.data(), stream.size(), plane, scale, max_iter, rms_eps);
     }
 
 private:
