@@ -75,19 +75,25 @@ class Quantizer:
         q = np.floor((v - self.min) / self.step)
         return np.minimum(float(self.max_quantized), q).astype(np.uint64)
 
+    def _values(self, codes) -> np.ndarray:
+        """fl(fl(q·step + min) + step/2) per code, the first rounding fused (one rounding of the exact rational)."""
+        step, mn, half = Fraction(self.step), Fraction(self.min), self.step / 2
+        fused = [float(int(q) * step + mn) for q in codes]
+        return np.array(fused, dtype=np.float64) + half
+
     def table(self) -> np.ndarray:
-        """value(q) for every code q (fl(fl(q·step + min) + step/2), the first rounding fused)."""
+        """value(q) for every code q: 2^bits rationals, for small `bits` only (value() does not need it)."""
         if self._table is None:
-            step, mn, half = Fraction(self.step), Fraction(self.min), self.step / 2
-            fused = [float(q * step + mn) for q in range(self.max_quantized + 1)]
-            self._table = np.array(fused, dtype=np.float64) + half
+            self._table = self._values(range(self.max_quantized + 1))
         return self._table
 
     def value(self, q) -> np.ndarray:
         q = np.asarray(q, dtype=np.uint64)
         if q.size and int(q.max()) > self.max_quantized:
             raise ValueError("Quantizer: code out of range (Quantizer.hpp:34)")
-        return self.table()[q.astype(np.int64)]
+        # only the codes present: a 24-bit field has 2^24 codes, a stream a few thousand of them
+        codes, inv = np.unique(q, return_inverse=True)
+        return self._values(codes)[inv.reshape(q.shape)]
 
 
 def psnr(a: np.ndarray, b: np.ndarray, peak: float = 255.0) -> float:

@@ -140,3 +140,76 @@ def test_quantized_decode_oracle_psnr(oracle):
     p_full, p_q = codec.psnr(src, dec_full), codec.psnr(src, dec_q)
     assert 25.0 < p_q <= p_full + 0.5, (p_full, p_q)
     assert codec.psnr(src, src) == float("inf")
+
+
+@pytest.mark.parametrize("bits", [2, 5, 7, 12])
+def test_quantizer_value_equals_table(bits):
+    # value() computes only the codes it is given; table() still computes all of them
+    q = codec.Quantizer(-1.2345678, 287.654321, bits)
+    codes = np.arange(1 << bits, dtype=np.uint64)
+    np.testing.assert_array_equal(q.value(codes), q.table()[codes.astype(np.int64)])
+    # repeated, unsorted and multi-dimensional arguments
+    pick = np.random.default_rng(bits).integers(0, 1 << bits, (3, 50)).astype(np.uint64)
+    got = q.value(pick)
+    assert got.shape == pick.shape and got.dtype == np.float64
+    np.testing.assert_array_equal(got, q.table()[pick.astype(np.int64)])
+    assert q.value(np.zeros(0, np.uint64)).shape == (0,)
+
+
+@pytest.mark.parametrize("bits", [20, 24])
+def test_wide_quantizer_matches_reference_build(oracle, bits):
+    rng = np.random.default_rng(bits)
+    lo, hi = sorted(rng.normal(0, 100, 2))
+    v = np.concatenate([[lo, hi], rng.uniform(lo, hi, 4000)])
+    ref = oracle.ref_quantize(lo, hi, bits, v)
+    if ref is None:
+        pytest.skip("oracle/_ref not built (no /root/reference here)")
+    q = codec.Quantizer(lo, hi, bits)
+    np.testing.assert_array_equal(q.quantized(v), ref[0])
+    np.testing.assert_array_equal(q.value(q.quantized(v)), ref[1])
+
+
+def _synth_cases():
+    from frc1_synth import FAST_STREAMS, OTHER_STREAMS
+
+    for k, (W, H, n, T, cb, bb, rb, _) in enumerate(FAST_STREAMS):
+        yield pytest.param(W, H, n, 2 * n, T, cb, bb, 0, 100 + k, rb, id=f"{W}x{H}-n{n}-{cb}+{bb}")
+    for k, (W, H, n, d, every) in enumerate(OTHER_STREAMS):
+        yield pytest.param(W, H, n, d, 8, 5, 7, every, 200 + k, None, id=f"{W}x{H}-n{n}-d{d}")
+
+
+@pytest.mark.parametrize("W,H,n,d,T,cb,bb,every,seed,record_bits", list(_synth_cases()))
+def test_synthetic_stream_roundtrip(W, H, n, d, T, cb, bb, every, seed, record_bits):
+    # the device decoder tests' streams (tests/test_gpu_frc1_shapes.py): bodies whose bit count is no multiple
+    # of 8 or of 32, records up to 64 bits, domain-less records, no domains, no ranges
+    import time
+
+    from frc1_synth import synth_items
+
+    items = synth_items(W, H, n, d, T, seed, empty_every=every)
+    buf = codec.pack_stream(items, W, H, n, d, transforms=T, contrast_bits=cb, brightness_bits=bb)
+    t0 = time.perf_counter()
+    back, h = codec.unpack_stream(buf)
+    assert time.perf_counter() - t0 < 1.0  # a 24 + 24-bit stream no longer builds 2^24-entry tables
+    widths = [h["index_bits"], max(1, (T - 1).bit_length()), cb, bb]
+    if record_bits is not None:
+        assert sum(widths) == record_bits
+    assert h["n_ranges"] == len(items) == (W // n) * (H // n)
+    assert len(buf) == codec.HEADER.size + (len(items) * sum(widths) + 7) // 8
+    for k in ("x", "y", "w", "h", "dx", "dy", "sw", "sh", "transform"):
+        np.testing.assert_array_equal(back[k], items[k], err_msg=k)
+    has = items["sw"] != 0
+    idx, t, qc, qb = codec._unpack_bits(buf[codec.HEADER.size:], len(items), widths)
+    dc = codec._grid_cols_rows(W, H, d, d // 2)[0]
+    np.testing.assert_array_equal(idx, np.where(has, (items["dy"] // (d // 2)) * dc + items["dx"] // (d // 2),
+                                                h["n_domains"]))
+    for field, codes, bits in (("contrast", qc, cb), ("brightness", qb, bb)):
+        v = items[field]
+        if len(v) and v.max() > v.min():
+            q = codec.Quantizer(v.min(), v.max(), bits)
+            np.testing.assert_array_equal(codes, q.quantized(v))
+            want = q.value(q.quantized(v))
+        else:
+            assert not codes.any()
+            want = v.copy()
+        np.testing.assert_array_equal(back[field], np.where(has, want, 0.0))

@@ -12,11 +12,10 @@ import pytest
 
 import fractencode_amd as F
 from fractencode_amd import codec
-from golden_util import oracle_records, plane
+from frc1_synth import oracle_decode_stream as _want, set_bits as _set_bits
+from golden_util import plane
 
 pytestmark = pytest.mark.gpu
-
-GEOMETRY = ("x", "y", "w", "h", "dx", "dy", "sw", "sh")
 
 
 def _search(p, n, T=4, cls=False, dsize=None, bits=((5, 7),)):
@@ -44,16 +43,6 @@ LENNA_BITS = ((5, 7), (7, 11), (9, 16))
 @functools.lru_cache(maxsize=None)
 def _lenna_streams(T):
     return _search(plane("lenna_y"), 8, T=T, bits=LENNA_BITS if T == 4 else ((5, 7),))[1]
-
-
-def _want(oracle, stream, scale=1, max_iter=-1, initial=None):
-    """The oracle's decode of the stream's records, scaled."""
-    rec, h = codec.unpack_stream(stream)
-    rec = rec.copy()
-    for k in GEOMETRY:
-        rec[k] *= scale
-    return oracle.decode(oracle_records(rec), scale * h["range_size"], scale * h["width"], scale * h["height"],
-                         max_iter=max_iter, initial=initial)
 
 
 def _same(got, want):
@@ -133,14 +122,6 @@ def test_degenerate_quantizer_field(oracle):
     assert h["contrast_min"] == h["contrast_max"] and h["brightness_min"] == h["brightness_max"]
     with F.Engine(0, 4) as e:
         _same(e.decode_frc1(s), _want(oracle, s))
-
-
-def _set_bits(buf, bit, width, value):
-    b = bytearray(buf)
-    for k in range(width):
-        byte, sh = codec.HEADER.size + (bit + k) // 8, (bit + k) % 8
-        b[byte] = (b[byte] & ~(1 << sh)) | (((value >> k) & 1) << sh)
-    return bytes(b)
 
 
 def test_rejections_leave_the_context_usable(oracle):
