@@ -296,6 +296,7 @@ struct frac_ctx {
     bool qt_dvalid[5] = {false, false, false, false, false};
     DBuf<uint8_t> d_sea_tmp;
     DBuf<unsigned long long> d_sea_count; // candidates the SEA search evaluated
+    DBuf<unsigned long long> d_tp_evals;  // tiled form: per group, the (range, domain) pairs of its window
     uint64_t eligible_pairs = 0;          // Σ over ranges of its bucket's domain count
     uint64_t evaluated_ran = 0;           // frac_stats.evaluated_mappings of the last run
     size_t sea_tmp_bytes = 0;
@@ -1137,8 +1138,9 @@ int prepare(frac_ctx* c)
         FRAC_HIP(c, c->d_tp_nch.ensure(ng + 1));
         FRAC_HIP(c, c->d_tp_choff.ensure(ng + 1));
         FRAC_HIP(c, c->d_tp_blkcnt.ensure(nbk + 1));
-        FRAC_HIP(c, c->d_tp_tot.ensure(4));
+        FRAC_HIP(c, c->d_tp_tot.ensure(6));
         FRAC_HIP(c, c->d_tp_pairs.ensure(std::max<size_t>(ng, 1)));
+        FRAC_HIP(c, c->d_tp_evals.ensure(std::max<size_t>(ng, 1)));
         FRAC_HIP(c, c->d_tp_rbk.ensure(std::max<size_t>(nr, 1)));
         FRAC_TRY(up(c->d_tp_groups.ptr, c->tp_groups.data(), ng * sizeof(uint4)));
         FRAC_TRY(up(c->d_tp_blk_group.ptr, c->tp_blk_group.data(), nbk * sizeof(uint2)));
@@ -2046,6 +2048,8 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing)
     w.work = c->d_m8_work.ptr;
     w.nchunks = c->d_tp_nch.ptr;
     w.pairs = c->d_tp_pairs.ptr;
+    w.bk = c->tp_bk;
+    w.evals = c->d_tp_evals.ptr;
     FRAC_HIP(c, hipMemsetAsync(c->d_tp_nch.ptr + ng, 0, sizeof(uint32_t), c->stream));
     tp_windows<<<(ng + 255) / 256, 256, 0, c->stream>>>(w);
     size_t tb = c->tp_tmp_bytes;
@@ -2059,18 +2063,19 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing)
                                                  (int)(nbk + 1), c->stream));
     // sizes of the entry arrays (total chunks, block → entry links) and the searched pairs: one copy
     tp_totals<<<1, 256, 0, c->stream>>>(c->d_tp_choff.ptr, ng, c->d_m8_blk_ptr.ptr, nbk, c->d_tp_pairs.ptr,
-                                        c->d_tp_tot.ptr);
-    uint32_t tot[4] = {0, 0, 0, 0};
+                                        c->d_tp_evals.ptr, c->d_tp_tot.ptr);
+    uint32_t tot[6] = {0, 0, 0, 0, 0, 0};
     FRAC_HIP(c, hipMemcpyAsync(tot, c->d_tp_tot.ptr, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
     FRAC_HIP(c, hipStreamSynchronize(c->stream));
     FRAC_HIP(c, c->d_m_entries.ensure(std::max<size_t>((size_t)tot[0] * kDftBlocksPerWG * 64, 1)));
     FRAC_HIP(c, c->d_m8_blk_ent.ensure(std::max<size_t>(tot[1], 1)));
     tp_fill_entries<<<(nbk + 255) / 256, 256, 0, c->stream>>>(c->d_tp_blk_group.ptr, c->d_tp_choff.ptr,
                                                               c->d_m8_blk_ptr.ptr, nbk, c->d_m8_blk_ent.ptr);
-    // issued matrix work (8 MFMA 32×32×16 per block × tile) and evaluated (slot, domain row) pairs
+    // issued matrix work (8 MFMA 32×32×16 per block × tile) and the (range, domain) pairs in the windows
+    // (padding slots and rows of partial blocks and tiles are no pairs)
     const uint64_t pairs = (uint64_t)tot[2] | ((uint64_t)tot[3] << 32);
     c->flops_ran = pairs * (kDftTpForm == 6 ? 6ull : 8ull) * 32768ull;
-    c->evaluated_ran = pairs * 32ull * 32ull;
+    c->evaluated_ran = (uint64_t)tot[4] | ((uint64_t)tot[5] << 32);
     da.m.entries = c->d_m_entries.ptr;
     da.choff = c->d_tp_choff.ptr;
     if (c->hitH > 0)
@@ -2921,6 +2926,7 @@ void frac_destroy(frac_ctx* c)
     c->d_tp_blkcnt.release();
     c->d_tp_tot.release();
     c->d_tp_pairs.release();
+    c->d_tp_evals.release();
     c->d_tp_row_of.release();
     c->d_tp_iota.release();
     c->d_tp_rbk.release();

@@ -220,7 +220,9 @@ struct TpWindowArgs {
     int64_t hitH;         // −1: no hits
     uint4* work;          // [ngroups] {first block, nblocks, t0, t1}
     uint32_t* nchunks;    // [ngroups]
-    uint32_t* pairs;      // [ngroups] block × tile pairs searched (frac_stats)
+    uint32_t* pairs;      // [ngroups] block × tile pairs searched (frac_stats.matrix_flops)
+    TpBuckets bk;
+    unsigned long long* evals; // [ngroups] (range, domain) pairs in the window (frac_stats.evaluated_mappings)
 };
 
 __global__ void __launch_bounds__(256) tp_windows(TpWindowArgs a)
@@ -264,29 +266,47 @@ __global__ void __launch_bounds__(256) tp_windows(TpWindowArgs a)
     a.work[gi] = make_uint4(gr.x, gr.y, t0, t1);
     a.nchunks[gi] = (t1 - t0 + 3) / 4;
     a.pairs[gi] = gr.y * (t1 - t0);
+    // the (range, domain) pairs among them: the bucket's last block and last tile are partly padding
+    uint32_t b = 0;
+    while (b + 1 < a.bk.nb && !(a.bk.tile_count[b] && a.bk.tile_first[b] == gr.z))
+        ++b;
+    const uint32_t slots = min(gr.y * 32u, a.bk.rng_count[b] - (gr.x - a.bk.blk_first[b]) * 32u);
+    const uint32_t r0 = (t0 - gr.z) * 32u, r1 = min((t1 - gr.z) * 32u, a.bk.dom_count[b]);
+    a.evals[gi] = (unsigned long long)slots * (r1 > r0 ? r1 - r0 : 0u);
 }
 
-// the totals the host needs in one 16-byte copy: {chunks, block → entry links, Σ pairs (u64)}
+// the totals the host needs in one 24-byte copy: {chunks, block → entry links, Σ pairs (u64), Σ evals (u64)}
 __global__ void __launch_bounds__(256) tp_totals(const uint32_t* __restrict__ choff, uint32_t ngroups,
                                                  const uint32_t* __restrict__ blk_ptr, uint32_t nblocks,
-                                                 const uint32_t* __restrict__ pairs, uint32_t* __restrict__ tot)
+                                                 const uint32_t* __restrict__ pairs,
+                                                 const unsigned long long* __restrict__ evals,
+                                                 uint32_t* __restrict__ tot)
 {
-    __shared__ unsigned long long part[4];
-    unsigned long long s = 0;
-    for (uint32_t g = threadIdx.x; g < ngroups; g += blockDim.x)
+    __shared__ unsigned long long part[2][4];
+    unsigned long long s = 0, v = 0;
+    for (uint32_t g = threadIdx.x; g < ngroups; g += blockDim.x) {
         s += pairs[g];
+        v += evals[g];
+    }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
+    for (int o = 32; o > 0; o >>= 1) {
         s += __shfl_xor(s, o, 64);
-    if ((threadIdx.x & 63u) == 0)
-        part[threadIdx.x >> 6] = s;
+        v += __shfl_xor(v, o, 64);
+    }
+    if ((threadIdx.x & 63u) == 0) {
+        part[0][threadIdx.x >> 6] = s;
+        part[1][threadIdx.x >> 6] = v;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const unsigned long long t = part[0] + part[1] + part[2] + part[3];
+        const unsigned long long t = part[0][0] + part[0][1] + part[0][2] + part[0][3];
+        const unsigned long long e = part[1][0] + part[1][1] + part[1][2] + part[1][3];
         tot[0] = choff[ngroups];
         tot[1] = blk_ptr[nblocks];
         tot[2] = (uint32_t)t;
         tot[3] = (uint32_t)(t >> 32);
+        tot[4] = (uint32_t)e;
+        tot[5] = (uint32_t)(e >> 32);
     }
 }
 
