@@ -1,0 +1,547 @@
+// fracenc_codec.hip — the decoders (items, a run's results, FRC1 streams), the FRC1 packer and parser,
+// and the colour conversion entry points.  Included by fracenc_api.hip.
+extern "C" {
+
+int frac_rgb_to_yuv_device(frac_ctx* c, const void* d_rgb, uint32_t w, uint32_t h, uint32_t rgb_stride, void* d_y,
+                           uint32_t y_stride, void* d_u, uint32_t u_stride, void* d_v, uint32_t v_stride)
+{
+    if (!c)
+        return FRAC_E_INVALID;
+    if (w == 0 || h == 0)
+        return FRAC_OK;
+    if (!d_rgb || !d_y || ((w >= 2 && h >= 2) && (!d_u || !d_v)) || rgb_stride < 3ull * w || y_stride < w ||
+        (w >= 2 && h >= 2 && (u_stride < w / 2 || v_stride < w / 2)))
+        return c->fail(FRAC_E_INVALID, "rgb_to_yuv: invalid plane pointers or strides");
+    FRAC_HIP(c, hipSetDevice(c->device));
+    ColorArgs a;
+    a.rgb = static_cast<const uint8_t*>(d_rgb);
+    a.w = w;
+    a.h = h;
+    a.rgb_stride = rgb_stride;
+    a.y = static_cast<uint8_t*>(d_y);
+    a.ys = y_stride;
+    a.u = static_cast<uint8_t*>(d_u);
+    a.us = u_stride;
+    a.v = static_cast<uint8_t*>(d_v);
+    a.vs = v_stride;
+    if (color_fast_path(a)) {
+        const size_t n = (size_t)(w / 4) * (h / 2);
+        rgb2yuv_quads4<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(a);
+    } else {
+        const size_t n = (size_t)((w + 1) / 2) * ((h + 1) / 2);
+        rgb2yuv_generic<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(a);
+    }
+    FRAC_HIP(c, hipGetLastError());
+    return FRAC_OK;
+}
+
+int frac_rgb_to_yuv(frac_ctx* c, const uint8_t* rgb, uint32_t w, uint32_t h, uint32_t rgb_stride, uint8_t* y,
+                    uint8_t* u, uint8_t* v)
+{
+    if (!c)
+        return FRAC_E_INVALID;
+    if (w == 0 || h == 0)
+        return FRAC_OK;
+    if (!rgb || !y || (w >= 2 && h >= 2 && (!u || !v)) || rgb_stride < 3ull * w)
+        return c->fail(FRAC_E_INVALID, "rgb_to_yuv: invalid buffers");
+    FRAC_HIP(c, hipSetDevice(c->device));
+    const uint32_t cw = w / 2, ch = h / 2;
+    const uint32_t ys = plane_pitch(w), cs = plane_pitch(cw);
+    const size_t rgb_bytes = (size_t)rgb_stride * h, y_bytes = (size_t)ys * h, c_bytes = (size_t)cs * std::max(ch, 1u);
+    FRAC_HIP(c, c->d_color.ensure(rgb_bytes + y_bytes + 2 * c_bytes));
+    uint8_t* d_rgb = c->d_color.ptr;
+    uint8_t* d_y = d_rgb + rgb_bytes;
+    uint8_t* d_u = d_y + y_bytes;
+    uint8_t* d_v = d_u + c_bytes;
+    FRAC_HIP(c, hipMemcpyAsync(d_rgb, rgb, rgb_bytes, hipMemcpyHostToDevice, c->stream));
+    FRAC_TRY(frac_rgb_to_yuv_device(c, d_rgb, w, h, rgb_stride, d_y, ys, d_u, cs, d_v, cs));
+    FRAC_HIP(c, hipMemcpy2DAsync(y, w, d_y, ys, w, h, hipMemcpyDeviceToHost, c->stream));
+    if (cw && ch) {
+        FRAC_HIP(c, hipMemcpy2DAsync(u, cw, d_u, cs, cw, ch, hipMemcpyDeviceToHost, c->stream));
+        FRAC_HIP(c, hipMemcpy2DAsync(v, cw, d_v, cs, cw, ch, hipMemcpyDeviceToHost, c->stream));
+    }
+    FRAC_HIP(c, hipStreamSynchronize(c->stream));
+    return FRAC_OK;
+}
+
+// Do the items (x, y, w, h) cover the w×h plane exactly once?  Checked on a bitmap of cells of
+// the smallest item size (every item a multiple of it, aligned), so O(cells), not O(pixels).
+static bool covers_exactly(const std::vector<frac_grid_item>& rects, uint32_t w, uint32_t h)
+{
+    if (rects.empty())
+        return false;
+    uint32_t g = ~0u;
+    for (const auto& r : rects) {
+        if (r.w == 0 || r.w != r.h)
+            return false;
+        g = std::min(g, r.w);
+    }
+    if (w % g || h % g)
+        return false;
+    const uint32_t cw = w / g, ch = h / g;
+    std::vector<uint8_t> cell((size_t)cw * ch, 0);
+    size_t covered = 0;
+    for (const auto& r : rects) {
+        if (r.x % g || r.y % g || r.w % g || (uint64_t)r.x + r.w > w || (uint64_t)r.y + r.h > h)
+            return false;
+        for (uint32_t y = r.y / g; y < (r.y + r.h) / g; ++y)
+            for (uint32_t x = r.x / g; x < (r.x + r.w) / g; ++x) {
+                if (cell[(size_t)y * cw + x]++)
+                    return false;
+                ++covered;
+            }
+    }
+    return covered == cell.size();
+}
+
+// The fused decoders' loop: `step(src, tgt, stride)` enqueues one iteration that writes every pixel of tgt
+// from src and adds its (source − new)² sums to the kDecodeSlots slots (decode_fused over items, frc1dec_step
+// over a stream's records); decode_check, the buffer swap and the host's look at the flag every few steps
+// are shared.
+extern "C++" template <class Step>
+static int decode_fused_loop(frac_ctx* c, uint32_t w, uint32_t h, int iters, double eps, uint8_t* plane,
+                             int* iterations, double* rms, Step&& step)
+{
+    const uint32_t stride = plane_pitch(w);
+    const size_t bytes = (size_t)stride * (h + 1);
+    FRAC_HIP(c, c->d_dec_src.ensure(bytes));
+    FRAC_HIP(c, c->d_dec_tgt.ensure(bytes));
+    FRAC_HIP(c, c->d_dec_part.ensure(kDecodeSlots));
+    FRAC_HIP(c, hipMemsetAsync(c->d_dec_part.ptr, 0, kDecodeSlots * sizeof(unsigned long long), c->stream));
+    FRAC_HIP(c, c->d_dec_state.ensure(1));
+    FRAC_HIP(c, c->h_dec_state.ensure());
+    uint8_t* buf[2] = {c->d_dec_src.ptr, c->d_dec_tgt.ptr};
+    FRAC_HIP(c, hipMemsetAsync(buf[0], 100, bytes, c->stream)); // Decoder2: source filled with 100
+    FRAC_HIP(c, hipMemsetAsync(buf[1], 0, bytes, c->stream));
+    FRAC_HIP(c, hipMemcpy2DAsync(buf[1], stride, plane, w, w, h, hipMemcpyHostToDevice, c->stream));
+    FRAC_HIP(c, hipMemsetAsync(c->d_dec_state.ptr, 0, sizeof(DecodeState), c->stream));
+    constexpr int kChunk = 8; // iterations enqueued between host checks of the convergence flag
+    int enq = 0;
+    while (enq < iters) {
+        const int stop = std::min(iters, enq + kChunk);
+        for (; enq < stop; ++enq) {
+            step(buf[enq & 1], buf[(enq + 1) & 1], stride);
+            decode_check<<<1, kDecodeSlots, 0, c->stream>>>(c->d_dec_part.ptr, (uint64_t)w * h, eps, enq, iters - 1,
+                                                            c->d_dec_state.ptr);
+        }
+        FRAC_HIP(c, hipMemcpyAsync(c->h_dec_state.ptr, c->d_dec_state.ptr, sizeof(DecodeState), hipMemcpyDeviceToHost,
+                                   c->stream));
+        FRAC_HIP(c, hipStreamSynchronize(c->stream));
+        if (c->h_dec_state->done)
+            break;
+    }
+    int it = 0;
+    double r = 0.0;
+    if (iters > 0) {
+        it = c->h_dec_state->iterations;
+        r = c->h_dec_state->rms;
+    }
+    // the final target: step `it` when the loop broke there, else step iters − 1
+    const int last = iters > 0 ? (c->h_dec_state->done ? it : iters - 1) : -1;
+    const uint8_t* fin = last >= 0 ? buf[(last + 1) & 1] : buf[1];
+    FRAC_HIP(c, hipMemcpy2DAsync(plane, w, fin, stride, w, h, hipMemcpyDeviceToHost, c->stream));
+    FRAC_HIP(c, hipStreamSynchronize(c->stream));
+    FRAC_HIP(c, hipGetLastError());
+    if (iterations)
+        *iterations = it;
+    if (rms)
+        *rms = r;
+    return FRAC_OK;
+}
+
+// Fused decode (fracenc_decode.hip decode_fused / decode_check): the items tile the plane.
+static int decode_fused_impl(frac_ctx* c, const frac_encode_item* d_items, size_t n, uint32_t w, uint32_t h,
+                             int iters, double eps, uint8_t* plane, int* iterations, double* rms)
+{
+    DecodeArgs a;
+    a.items = d_items;
+    a.n = (uint32_t)n;
+    const uint32_t nblk = (uint32_t)((n + 3) / 4);
+    return decode_fused_loop(c, w, h, iters, eps, plane, iterations, rms,
+                             [&](const uint8_t* src, uint8_t* tgt, uint32_t stride) {
+                                 a.src = src;
+                                 a.tgt = tgt;
+                                 a.stride = stride;
+                                 decode_fused<<<nblk, 256, 0, c->stream>>>(a, c->d_dec_state.ptr, c->d_dec_part.ptr);
+                             });
+}
+
+static int decode_impl(frac_ctx* c, const frac_encode_item* d_items, size_t n, uint32_t w, uint32_t h, int max_iter,
+                       double eps, uint8_t* plane, int* iterations, double* rms, bool fused = false)
+{
+    if (!plane || w == 0 || h == 0)
+        return c->fail(FRAC_E_INVALID, "decode: invalid plane");
+    FRAC_TRY(check_ab_knobs(c));
+    if (fused &&!(c->p.flags & FRAC_FLAG_DECODE_STEPWISE) && ab_knob("FRAC_DECODE_UNFUSED") == nullptr)
+        return decode_fused_impl(c, d_items, n, w, h, max_iter < 0 ? 300 : max_iter, eps, plane, iterations, rms);
+    const uint32_t stride = plane_pitch(w);
+    const size_t bytes = (size_t)stride * (h + 1);
+    FRAC_HIP(c, c->d_dec_src.ensure(bytes));
+    FRAC_HIP(c, c->d_dec_tgt.ensure(bytes));
+    FRAC_HIP(c, c->d_dec_sum.ensure(1));
+    FRAC_HIP(c, c->h_dec_sum.ensure());
+    // Decoder2::decode: source filled with 100, target = the caller's plane
+    FRAC_HIP(c, hipMemsetAsync(c->d_dec_src.ptr, 100, bytes, c->stream));
+    FRAC_HIP(c, hipMemsetAsync(c->d_dec_tgt.ptr, 0, bytes, c->stream));
+    FRAC_HIP(c, hipMemcpy2DAsync(c->d_dec_tgt.ptr, stride, plane, w, w, h, hipMemcpyHostToDevice, c->stream));
+    const int iters = max_iter < 0 ? 300 : max_iter;
+    DecodeArgs a;
+    a.src = c->d_dec_src.ptr;
+    a.tgt = c->d_dec_tgt.ptr;
+    a.stride = stride;
+    a.items = d_items;
+    a.n = (uint32_t)n;
+    const uint32_t rms_blocks = (uint32_t)std::min<size_t>(1024, ((size_t)w * h + 255) / 256);
+    int i = 0;
+    double r = 0.0;
+    for (; i < iters; ++i) {
+        if (n)
+            decode_apply<<<(unsigned)((n + 3) / 4), 256, 0, c->stream>>>(a);
+        FRAC_HIP(c, hipMemsetAsync(c->d_dec_sum.ptr, 0, sizeof(unsigned long long), c->stream));
+        decode_rms<<<rms_blocks, 256, 0, c->stream>>>(c->d_dec_src.ptr, c->d_dec_tgt.ptr, w, h, stride, c->d_dec_sum.ptr);
+        FRAC_HIP(c, hipMemcpyAsync(c->h_dec_sum.ptr, c->d_dec_sum.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                   c->stream));
+        FRAC_HIP(c, hipStreamSynchronize(c->stream));
+        // the reference accumulates in int32 (metrics.h:29): reproduce its wrap-around
+        const int32_t s32 = (int32_t)(uint32_t)(*c->h_dec_sum.ptr & 0xffffffffull);
+        r = (double)s32 / (double)((uint64_t)w * h);
+        if (r < eps)
+            break;
+        FRAC_HIP(c, hipMemcpyAsync(c->d_dec_src.ptr, c->d_dec_tgt.ptr, bytes, hipMemcpyDeviceToDevice, c->stream));
+    }
+    FRAC_HIP(c, hipMemcpy2DAsync(plane, w, c->d_dec_tgt.ptr, stride, w, h, hipMemcpyDeviceToHost, c->stream));
+    FRAC_HIP(c, hipStreamSynchronize(c->stream));
+    FRAC_HIP(c, hipGetLastError());
+    if (iterations)
+        *iterations = i;
+    if (rms)
+        *rms = r;
+    return FRAC_OK;
+}
+
+int frac_decode(frac_ctx* c, const frac_encode_item* items, size_t n, uint32_t w, uint32_t h, int max_iter,
+                double rms_eps, uint8_t* plane, int* iterations, double* rms)
+{
+    if (!c)
+        return FRAC_E_INVALID;
+    if (n && !items)
+        return c->fail(FRAC_E_INVALID, "decode: items is NULL");
+    for (size_t i = 0; i < n; ++i) {
+        const frac_encode_item& e = items[i];
+        if ((uint64_t)e.x + e.w > w || (uint64_t)e.y + e.h > h || e.match.score.transform < 0 ||
+            e.match.score.transform > 7 ||
+            (e.match.sw && ((uint64_t)e.match.x + e.match.sw > w || (uint64_t)e.match.y + e.match.sh > h)))
+            return c->fail(FRAC_E_INVALID, "decode: item outside the plane or bad transform");
+        // a rectangular (or degenerate) domain: the transformed 2×2 samples (Frac::copy's fit points,
+        // DecodeUtils.hpp:9-25) may leave the patch; they must stay inside the plane
+        if (e.match.sw && (e.match.sw != e.match.sh || e.match.sw < 2) &&
+            (e.match.sw < 2 || e.match.sh < 2 || e.w == 0 || e.h == 0 ||
+             !box_inside(sample_box(e.match.score.transform, (int)e.match.sw, (int)e.match.sh, (int)e.w, (int)e.h,
+                                    false, true),
+                         e.match.x, e.match.y, w, h)))
+            return c->fail(FRAC_E_INVALID, "decode: a transformed sample of item " + std::to_string(i) +
+                                               " falls outside the plane");
+    }
+    FRAC_HIP(c, hipSetDevice(c->device));
+    FRAC_HIP(c, c->d_dec_items.ensure(n));
+    if (n)
+        FRAC_HIP(c, hipMemcpyAsync(c->d_dec_items.ptr, items, n * sizeof(frac_encode_item), hipMemcpyHostToDevice,
+                                   c->stream));
+    std::vector<frac_grid_item> rects(n);
+    bool all_domains = true;
+    for (size_t i = 0; i < n; ++i) {
+        rects[i] = frac_grid_item{items[i].x, items[i].y, items[i].w, items[i].h, -1};
+        all_domains = all_domains && items[i].match.sw != 0 && items[i].match.sh != 0;
+    }
+    const bool fused = all_domains && covers_exactly(rects, w, h);
+    return decode_impl(c, c->d_dec_items.ptr, n, w, h, max_iter, rms_eps, plane, iterations, rms, fused);
+}
+
+int frac_decode_results(frac_ctx* c, uint32_t w, uint32_t h, int max_iter, double rms_eps, uint8_t* plane,
+                        int* iterations, double* rms)
+{
+    if (!c)
+        return FRAC_E_INVALID;
+    if (!c->ran)
+        return c->fail(FRAC_E_STATE, "decode: frac_run has not been called");
+    if (c->src.w > w || c->src.h > h || c->tgt.w > w || c->tgt.h > h)
+        return c->fail(FRAC_E_INVALID, "decode: plane smaller than the encoded planes");
+    FRAC_HIP(c, hipSetDevice(c->device));
+    FRAC_TRY(settle_fallback(c));
+    // the fused form needs every range written: no empty (domain-less) record among the results
+    bool fused = covers_exactly(c->ranges, w, h);
+    if (fused && !c->ranges.empty()) {
+        c->h_aux.resize(nranges(c));
+        FRAC_HIP(c, hipMemcpyAsync(c->h_aux.data(), c->d_aux.ptr, nranges(c) * sizeof(RangeAux),
+                                   hipMemcpyDeviceToHost, c->stream));
+        FRAC_HIP(c, hipStreamSynchronize(c->stream));
+        for (const RangeAux& x : c->h_aux)
+            if (x.flags & kAuxEmpty) {
+                fused = false;
+                break;
+            }
+    }
+    return decode_impl(c, c->d_out.ptr, nranges(c), w, h, max_iter, rms_eps, plane, iterations, rms, fused);
+}
+
+int frac_pack_frc1(frac_ctx* c, uint32_t cbits, uint32_t bbits, uint8_t* out, size_t cap, size_t* n_out)
+{
+    if (!c)
+        return FRAC_E_INVALID;
+    if (!n_out)
+        return c->fail(FRAC_E_INVALID, "pack_frc1: n_out is NULL");
+    if (!c->ran)
+        return c->fail(FRAC_E_STATE, "pack_frc1: frac_run has not been called");
+    if (cbits < 2 || cbits > 16 || bbits < 2 || bbits > 16)
+        return c->fail(FRAC_E_INVALID, "pack_frc1: contrast/brightness bits must be in [2, 16]");
+    const uint32_t W = c->tgt.w, H = c->tgt.h, n = (uint32_t)c->n;
+    if (c->src.w != W || c->src.h != H)
+        return c->fail(FRAC_E_INVALID, "pack_frc1: source and target planes must have one size");
+    // the stream's implicit geometry: createUniformGrid ranges (row-major) and domains
+    // (compared item by item against the closed-form lattice, without building it: at C3 the two grids
+    // hold 0.5 M items)
+    auto same_grid = [&](const std::vector<frac_grid_item>& g, uint32_t size, uint32_t off) {
+        const size_t cnt = frac_uniform_grid(W, H, size, off, nullptr, 0);
+        if (cnt != g.size())
+            return false;
+        if (!cnt)
+            return true;
+        const size_t cols = (W - size) / off + 1;
+        const frac_grid_item* it = g.data();
+        for (size_t r = 0, k = 0; k < cnt; ++r)
+            for (size_t q = 0; q < cols; ++q, ++k, ++it)
+                if (it->x != q * off || it->y != r * off || it->w != size || it->h != size)
+                    return false;
+        return true;
+    };
+    if (n == 0)
+        return c->fail(FRAC_E_INVALID, "pack_frc1: the stream holds square items only");
+    if (!same_grid(c->ranges, n, n))
+        return c->fail(FRAC_E_INVALID, "pack_frc1: ranges are not the row-major range grid");
+    if (!same_grid(c->doms, 2 * n, n))
+        return c->fail(FRAC_E_INVALID, "pack_frc1: domains are not the domain lattice (size 2n, stride n)");
+    const uint32_t nr = (uint32_t)nranges(c), nd = (uint32_t)c->doms.size(), T = c->p.transforms;
+    auto bitlen = [](uint64_t v) { uint32_t b = 0; while (v) { ++b; v >>= 1; } return b; };
+    const uint32_t ib = std::max(1u, bitlen(nd)), tb = std::max(1u, bitlen(T - 1));
+    const uint32_t width = ib + tb + cbits + bbits;
+    if (width > 64)
+        return c->fail(FRAC_E_INVALID, "pack_frc1: record wider than 64 bits");
+    const uint64_t body = ((uint64_t)nr * width + 7) / 8, nwords = ((uint64_t)nr * width + 31) / 32;
+    *n_out = FRAC_FRC1_HEADER_BYTES + body;
+    if (!out)
+        return FRAC_OK;
+    FRAC_HIP(c, hipSetDevice(c->device));
+    FRAC_TRY(settle_fallback(c));
+    Frc1MinMax mm{~0ull, 0ull, ~0ull, 0ull};
+    std::vector<uint32_t> words(nwords);
+    if (nr) {
+        FRAC_HIP(c, c->d_frc_mm.ensure(1));
+        FRAC_HIP(c, c->d_frc_rec.ensure(nr));
+        FRAC_HIP(c, c->d_frc_words.ensure(nwords));
+        FRAC_HIP(c, hipMemsetAsync(c->d_frc_mm.ptr, 0xff, sizeof(unsigned long long), c->stream));
+        FRAC_HIP(c, hipMemsetAsync(&c->d_frc_mm.ptr->cmax, 0, sizeof(unsigned long long), c->stream));
+        FRAC_HIP(c, hipMemsetAsync(&c->d_frc_mm.ptr->bmin, 0xff, sizeof(unsigned long long), c->stream));
+        FRAC_HIP(c, hipMemsetAsync(&c->d_frc_mm.ptr->bmax, 0, sizeof(unsigned long long), c->stream));
+        frc1_minmax<<<std::min<uint32_t>(1024, (nr + 255) / 256), 256, 0, c->stream>>>(c->d_out.ptr, nr,
+                                                                                          c->d_frc_mm.ptr);
+        Frc1Args a;
+        a.out = c->d_out.ptr;
+        a.n = nr;
+        a.dstride = n;
+        a.dcols = (uint32_t)((W - 2 * n) / n + 1);
+        a.ndomains = nd;
+        a.index_bits = ib;
+        a.t_bits = tb;
+        a.c_bits = cbits;
+        a.b_bits = bbits;
+        a.mm = c->d_frc_mm.ptr;
+        a.rec = c->d_frc_rec.ptr;
+        frc1_records<<<(nr + 255) / 256, 256, 0, c->stream>>>(a);
+        frc1_words<<<(unsigned)((nwords + 255) / 256), 256, 0, c->stream>>>(c->d_frc_rec.ptr, nr, width, nwords,
+                                                                             c->d_frc_words.ptr);
+        FRAC_HIP(c, hipGetLastError());
+        FRAC_HIP(c, hipMemcpyAsync(&mm, c->d_frc_mm.ptr, sizeof(mm), hipMemcpyDeviceToHost, c->stream));
+        FRAC_HIP(c, hipMemcpyAsync(words.data(), c->d_frc_words.ptr, nwords * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                   c->stream));
+        FRAC_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    // header "<4sHHIIIIIBBBBIIdddd" (fractencode_amd/codec.py)
+    uint8_t hdr[FRAC_FRC1_HEADER_BYTES] = {};
+    size_t o = 0;
+    auto put = [&](const void* v, size_t k) { std::memcpy(hdr + o, v, k); o += k; };
+    const uint16_t version = 1, flags = c->p.use_classifier ? 1 : 0;
+    const uint32_t u32s[5] = {W, H, n, 2 * n, n};
+    const uint8_t u8s[4] = {(uint8_t)T, (uint8_t)cbits, (uint8_t)bbits, (uint8_t)ib};
+    const uint32_t counts[2] = {nr, nd};
+    const double mm_d[4] = {nr ? dkey_inv(mm.cmin) : 0.0, nr ? dkey_inv(mm.cmax) : 0.0, nr ? dkey_inv(mm.bmin) : 0.0,
+                            nr ? dkey_inv(mm.bmax) : 0.0};
+    put("FRC1", 4);
+    put(&version, 2);
+    put(&flags, 2);
+    put(u32s, sizeof(u32s));
+    put(u8s, sizeof(u8s));
+    put(counts, sizeof(counts));
+    put(mm_d, sizeof(mm_d));
+    const size_t total = FRAC_FRC1_HEADER_BYTES + body;
+    std::memcpy(out, hdr, std::min<size_t>(cap, FRAC_FRC1_HEADER_BYTES));
+    if (cap > FRAC_FRC1_HEADER_BYTES)
+        std::memcpy(out + FRAC_FRC1_HEADER_BYTES, words.data(), std::min<size_t>(cap, total) - FRAC_FRC1_HEADER_BYTES);
+    return FRAC_OK;
+}
+
+// The FRC1 header "<4sHHIIIIIBBBBIIdddd" (fractencode_amd/codec.py) parsed and checked against the stream
+// length; on failure `msg` names the rule.
+using Frc1Info = struct frac_frc1_info; // the plain name is the function's
+static int frc1_parse(const uint8_t* s, size_t len, Frc1Info* o, std::string& msg)
+{
+    auto bad = [&](const char* why) {
+        msg = std::string("FRC1: ") + why;
+        return FRAC_E_INVALID;
+    };
+    if (!s || !o)
+        return bad("NULL argument");
+    if (len < FRAC_FRC1_HEADER_BYTES)
+        return bad("truncated header");
+    uint16_t version, flags;
+    uint32_t u[5], counts[2];
+    double mm[4];
+    std::memcpy(&version, s + 4, 2);
+    std::memcpy(&flags, s + 6, 2);
+    std::memcpy(u, s + 8, sizeof(u));
+    std::memcpy(counts, s + 32, sizeof(counts));
+    std::memcpy(mm, s + 40, sizeof(mm));
+    if (std::memcmp(s, "FRC1", 4) != 0 || version != 1)
+        return bad("bad magic or version");
+    *o = Frc1Info{};
+    o->width = u[0], o->height = u[1], o->range_size = u[2], o->domain_size = u[3], o->domain_stride = u[4];
+    o->transforms = s[28], o->contrast_bits = s[29], o->brightness_bits = s[30], o->index_bits = s[31];
+    o->n_ranges = counts[0], o->n_domains = counts[1], o->flags = flags;
+    o->contrast_min = mm[0], o->contrast_max = mm[1], o->brightness_min = mm[2], o->brightness_max = mm[3];
+    if (o->width == 0 || o->height == 0 || o->range_size == 0)
+        return bad("zero width, height or range size");
+    if (o->domain_size < 2 || (o->domain_size & 1u) || o->domain_stride != o->domain_size / 2)
+        return bad("domain size must be even and at least 2, its stride half of it");
+    if (o->transforms < 1 || o->transforms > 8)
+        return bad("transforms outside 1..8");
+    if (o->contrast_bits < 2 || o->contrast_bits > 24 || o->brightness_bits < 2 || o->brightness_bits > 24)
+        return bad("contrast / brightness bits outside [2, 24]");
+    auto bitlen = [](uint64_t v) { uint32_t b = 0; while (v) { ++b; v >>= 1; } return b; };
+    if (o->index_bits != std::max(1u, bitlen(o->n_domains)))
+        return bad("index bits do not match the domain count");
+    o->record_bits = o->index_bits + std::max(1u, bitlen(o->transforms - 1)) + o->contrast_bits + o->brightness_bits;
+    if (o->record_bits > 64)
+        return bad("record wider than 64 bits");
+    if (o->n_ranges != frac_uniform_grid(o->width, o->height, o->range_size, o->range_size, nullptr, 0))
+        return bad("range count is not the range grid's");
+    if (o->n_domains != frac_uniform_grid(o->width, o->height, o->domain_size, o->domain_stride, nullptr, 0))
+        return bad("domain count is not the domain grid's");
+    o->body_bytes = ((uint64_t)o->n_ranges * o->record_bits + 7) / 8;
+    if (len - FRAC_FRC1_HEADER_BYTES < o->body_bytes)
+        return bad("truncated records");
+    for (double v : mm)
+        if (!std::isfinite(v))
+            return bad("non-finite quantizer bound");
+    return FRAC_OK;
+}
+
+int frac_frc1_info(const uint8_t* stream, size_t len, struct frac_frc1_info* out)
+{
+    std::string msg;
+    const int rc = frc1_parse(stream, len, out, msg);
+    if (rc != FRAC_OK)
+        g_last_error = msg;
+    return rc;
+}
+
+int frac_decode_frc1(frac_ctx* c, const uint8_t* stream, size_t len, uint32_t scale, int max_iter, double rms_eps,
+                     uint8_t* plane, size_t plane_bytes, int* iterations, double* rms)
+{
+    if (!c)
+        return FRAC_E_INVALID;
+    Frc1Info h;
+    {
+        std::string msg;
+        if (frc1_parse(stream, len, &h, msg) != FRAC_OK)
+            return c->fail(FRAC_E_INVALID, msg);
+    }
+    FRAC_TRY(check_ab_knobs(c));
+    if (scale < 1 || scale > 16 || (uint64_t)scale * h.width > 65535 || (uint64_t)scale * h.height > 65535)
+        return c->fail(FRAC_E_INVALID, "decode_frc1: scale must be in 1..16 and the scaled frame at most 65535 a side");
+    const uint32_t W = scale * h.width, H = scale * h.height;
+    if (!plane || plane_bytes < (uint64_t)W * H)
+        return c->fail(FRAC_E_INVALID, "decode_frc1: the plane is smaller than the scaled frame");
+    const uint32_t n = h.n_ranges;
+    Frc1Layout L{};
+    L.n_ranges = n;
+    L.n_domains = h.n_domains;
+    L.rcols = n ? (h.width - h.range_size) / h.range_size + 1 : 0;
+    L.dcols = h.n_domains ? (h.width - h.domain_size) / h.domain_stride + 1 : 0;
+    L.range_size = h.range_size;
+    L.domain_size = h.domain_size;
+    L.domain_stride = h.domain_stride;
+    L.index_bits = h.index_bits;
+    L.c_bits = h.contrast_bits;
+    L.b_bits = h.brightness_bits;
+    L.t_bits = h.record_bits - h.index_bits - h.contrast_bits - h.brightness_bits;
+    L.record_bits = h.record_bits;
+    // Quantizer (encode/Quantizer.hpp:19-22): step = |max − min| / 2^bits; !(max > min): every code is min
+    auto step = [](double lo, double hi, uint32_t bits) {
+        return hi > lo ? std::fabs(hi - lo) / (double)(1u << bits) : 0.0;
+    };
+    L.c_step = step(h.contrast_min, h.contrast_max, h.contrast_bits);
+    L.c_min = h.contrast_min;
+    L.b_step = step(h.brightness_min, h.brightness_max, h.brightness_bits);
+    L.b_min = h.brightness_min;
+
+    FRAC_HIP(c, hipSetDevice(c->device));
+    // record pass: reads only the stream buffer (the body and kFrc1PadWords zeroed dwords after it)
+    uint32_t status[2] = {0, 0};
+    if (n) {
+        const size_t body_words = (size_t)((h.body_bytes + 3) / 4);
+        FRAC_HIP(c, c->d_frc_in.ensure(body_words + kFrc1PadWords));
+        FRAC_HIP(c, c->d_frc_rec.ensure(n));
+        FRAC_HIP(c, c->d_frc_status.ensure(2));
+        // from the body's last whole dword on: its tail bytes and the padding
+        FRAC_HIP(c, hipMemsetAsync(c->d_frc_in.ptr + (body_words - 1), 0, (1 + kFrc1PadWords) * sizeof(uint32_t),
+                                   c->stream));
+        FRAC_HIP(c, hipMemsetAsync(c->d_frc_status.ptr, 0, sizeof(status), c->stream));
+        FRAC_HIP(c, hipMemcpyAsync(c->d_frc_in.ptr, stream + FRAC_FRC1_HEADER_BYTES, (size_t)h.body_bytes,
+                                   hipMemcpyHostToDevice, c->stream));
+        frc1dec_records<<<(n + 255) / 256, 256, 0, c->stream>>>(c->d_frc_in.ptr, L, c->d_frc_rec.ptr,
+                                                                 c->d_frc_status.ptr);
+        FRAC_HIP(c, hipGetLastError());
+        FRAC_HIP(c, hipMemcpyAsync(status, c->d_frc_status.ptr, sizeof(status), hipMemcpyDeviceToHost, c->stream));
+        FRAC_HIP(c, hipStreamSynchronize(c->stream));
+        if (status[0])
+            return c->fail(FRAC_E_INVALID, "FRC1: domain index out of range");
+    }
+    const bool tiles = n && h.width % h.range_size == 0 && h.height % h.range_size == 0 && status[1] == 0;
+    if (tiles && h.domain_size == 2 * h.range_size && !(c->p.flags & FRAC_FLAG_DECODE_STEPWISE)) {
+        Frc1StepArgs a;
+        a.w = W;
+        a.h = H;
+        a.R = scale * h.range_size;
+        a.rrows = h.height / h.range_size;
+        a.scale = scale;
+        a.rec = c->d_frc_rec.ptr;
+        const dim3 grid((W + kFrc1TileW - 1) / kFrc1TileW, (H + kFrc1TileH - 1) / kFrc1TileH);
+        return decode_fused_loop(c, W, H, max_iter < 0 ? 300 : max_iter, rms_eps, plane, iterations, rms,
+                                 [&](const uint8_t* src, uint8_t* tgt, uint32_t stride) {
+                                     a.src = src;
+                                     a.tgt = tgt;
+                                     a.stride = stride;
+                                     frc1dec_step<<<grid, 256, 0, c->stream>>>(a, L, c->d_dec_state.ptr,
+                                                                               c->d_dec_part.ptr);
+                                 });
+    }
+    // every other stream: the records as scaled encode items, through the item decoder (fused when they
+    // tile the plane and every range has a domain, as frac_decode decides)
+    FRAC_HIP(c, c->d_dec_items.ensure(n));
+    if (n) {
+        frc1dec_expand<<<(n + 255) / 256, 256, 0, c->stream>>>(c->d_frc_rec.ptr, L, scale, c->d_dec_items.ptr);
+        FRAC_HIP(c, hipGetLastError());
+    }
+    return decode_impl(c, c->d_dec_items.ptr, n, W, H, max_iter, rms_eps, plane, iterations, rms, tiles);
+}
+
+} // extern "C"

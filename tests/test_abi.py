@@ -151,7 +151,7 @@ def _kernel_instances(pattern):
 
 def test_product_library_has_no_ablation_kernels():
     # the "tuning only, wrong results" ablations exist only in a -DFRAC_TUNING build; unknown or
-    # ablation FRAC_MFMA_VARIANT values fail the run (fracenc_api.hip mfma_variant)
+    # ablation FRAC_MFMA_VARIANT values fail the run (fracenc_launch.hip mfma_variant)
     dft = _kernel_instances(r"fracenc::search_dft<(?:true|false), (\d+)")
     mfma = _kernel_instances(r"fracenc::search_mfma<\d+, \d+, (?:true|false), (\d+)>")
     assert dft and mfma

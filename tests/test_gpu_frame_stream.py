@@ -109,6 +109,55 @@ def test_streamed_frames_equal_synchronous_searches(cls):
         np.testing.assert_array_equal(fields[k], rec[k], err_msg=k)
 
 
+def test_context_closed_with_work_in_flight(oracle):
+    """An engine closed right after it enqueued work (no sync, no fetch): the context goes idle on its streams
+    before any of its buffers, pinned objects, events or streams is released, so a second engine opened on the
+    same device at once searches the crop exactly as the oracle does.  Eight rounds over four enqueue-only
+    sequences: a streamed frame and a run, a device-planned quadtree frame, a run packed and decoded as FRC1,
+    and a run with a tuple sink."""
+    import torch
+
+    p = np.fromfile(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "crop64.u8"),
+                    dtype=np.uint8).reshape(64, 64)
+    doms = F.create_uniform_grid(64, 64, 16, 8)
+    rngs = F.create_uniform_grid(64, 64, 8, 8)
+    want, _, _ = oracle.estimate(p, oracle.uniform_grid(64, 64, 16, 8), oracle.uniform_grid(64, 64, 8, 8))
+    host = torch.from_numpy(p.copy()).pin_memory()
+    sink = torch.zeros(len(rngs) * F.TUPLE.itemsize, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+
+    def streamed_frame(e):
+        e.set_frame_async(host)
+        e.run()
+
+    def quadtree_frame(e):
+        e.encode_quadtree(16, 4, 10.0)
+
+    def frc1_round_trip(e):
+        e.run()
+        e.decode_frc1(e.pack_frc1())
+
+    def run_into_sink(e):
+        e.set_tuple_sink(sink.data_ptr())
+        e.run()
+
+    sequences = [streamed_frame, quadtree_frame, frc1_round_trip, run_into_sink]
+    for k in range(8):
+        first = F.Engine(0, 4)
+        first.set_frame(p)
+        first.set_domains(doms)
+        first.set_ranges(rngs)
+        sequences[k % 4](first)
+        first.close()
+        with F.Engine(0, 4) as second:
+            second.set_frame(p)
+            second.set_domains(doms)
+            out, _ = second.search(rngs)
+        for a, b in (("dx", "dx"), ("dy", "dy"), ("transform", "t"), ("distance", "dist"), ("contrast", "s"),
+                     ("brightness", "o")):
+            np.testing.assert_array_equal(out[a], want[b], err_msg=f"round {k}: {a}")
+
+
 def test_set_frame_device_async_rejects_host_planes():
     with F.Engine(0) as e:
         with pytest.raises(F.FracError):

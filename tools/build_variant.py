@@ -3,7 +3,8 @@
 tree is untouched): each SUB is FILE:OLD=>NEW, an exact one-time replacement in csrc/FILE.  The
 library goes to OUT (use it with FRAC_LIB=OUT in tools/bench_paths.py; bench.py refuses a foreign
 library for its headline).
-usage: tools/build_variant.py [--git REV] OUT.so 'fracenc_api.hip:old text=>new text' [...]"""
+usage: tools/build_variant.py [--git REV] OUT.so 'fracenc_launch.hip:old text=>new text' [...]
+(FILE is any file of csrc/: a kernel file or the host layer's fracenc_ctx.h, _plan, _launch, _quadtree, _codec, _api)"""
 import os
 import shutil
 import subprocess

@@ -6,7 +6,7 @@ synchronised): the search, the 32-byte tuple pack of the shard (frac_copy_tuples
 world-1 RCCL all_gather_into_tensor of the padded shard on the engine's stream — the collective's
 launch and copy on this GPU; the xGMI transfer of the other ranks' shards is not in it.  The
 slowest shard bounds the N-GPU step.  Also printed: the search's workgroup count per shard
-(prepare()'s build_work rule, fracenc_api.hip), which must stay well above the 256 CUs × 2
+(build_work(), fracenc_plan.hip: prepare()'s work-list rule), which must stay well above the 256 CUs × 2
 workgroups the 8-wave search keeps resident.  The scaling curve itself is the driver's
 (SCALE_rNN.json); this is a per-shard prediction, not a claim.
 usage: tools/shard_sim.py [N ...]   (default 1 2 4 8)"""
@@ -24,7 +24,7 @@ from fractencode_amd.synth import value_noise  # noqa: E402
 
 
 def search_wgs(nranges: int, ndoms: int, bpw: int = 8, target: int = 8192 // 8 * 4) -> int:
-    """Workgroups of the 8-wave Fourier search for one bucket (build_work in fracenc_api.hip)."""
+    """Workgroups of the 8-wave Fourier search for one bucket (build_work() in fracenc_plan.hip, one bucket)."""
     blocks = (nranges + 31) // 32
     tiles = (ndoms + 31) // 32
     groups = (blocks + bpw - 1) // bpw
