@@ -72,6 +72,8 @@ FLAG_TIMING = 1
 # alternative exact forms (ABI 6; the product build refuses the old FRAC_MFMA_DFT / FRAC_SEA_TILED /
 # FRAC_DECODE_UNFUSED environment knobs)
 FLAG_DIRECT_FORM, FLAG_SEA_PER_RANGE, FLAG_DECODE_STEPWISE = 2, 4, 8
+# ENGINE_AUTO's pruned route (n = 8, T = 4, ratio 2): never / whenever the geometry allows it
+FLAG_EXHAUSTIVE, FLAG_PRUNE = 16, 32
 
 # Frac::TransformType (image/transform.h:16-25)
 TRANSFORM_NAMES = ("Id", "Rotate_90", "Rotate_180", "Rotate_270", "Flip", "Flip_Rotate_90", "Flip_Rotate_180",
@@ -305,7 +307,8 @@ class Engine:
                  rms_threshold: float = 0.0, s_max: float = -1.0, engine: int = ENGINE_AUTO, timing: bool = False,
                  flags: int = 0):
         """flags: FLAG_DIRECT_FORM / FLAG_SEA_PER_RANGE / FLAG_DECODE_STEPWISE select an alternative
-        exact form (the same records from other kernels: cross-checks)."""
+        exact form (the same records from other kernels: cross-checks); FLAG_EXHAUSTIVE / FLAG_PRUNE keep
+        ENGINE_AUTO off / put it on its pruned route (n = 8, T = 4) whatever the run's size."""
         self._p = FracParams(transforms, int(use_classifier), rms_threshold, s_max, engine,
                              (FLAG_TIMING if timing else 0) | flags)
         self._ctx = lib().frac_create(device, C.byref(self._p))

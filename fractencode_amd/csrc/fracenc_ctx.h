@@ -231,6 +231,17 @@ struct frac_ctx {
     DBuf<uint4> d_tp_groups;
     DBuf<uint2> d_tp_blk_group, d_tp_tile_sd, d_tp_blk_sr;
     DBuf<uint32_t> d_tp_blk_u, d_tp_nch, d_tp_choff, d_tp_blkcnt, d_tp_tot, d_tp_iota, d_tp_pairs, d_tp_row_of;
+    // the tiled form's own maps and work lists, in its sorted layout (rebuilt every run): under AUTO the
+    // MFMA engine's domain-ordered ones (d_m_tile_pos, the slot maps, d_m8_*) stay prepared beside them
+    DBuf<int32_t> d_tp_slot_range, d_tp_tile_pos;
+    DBuf<uint32_t> d_tp_range_slot, d_tp_blk_ptr, d_tp_blk_ent;
+    DBuf<uint4> d_tp_work;
+    DBuf<unsigned long long> d_tp_sevals; // per group, the (range, domain) pairs of its seed tile
+    // FRAC_ENGINE_AUTO's pruned route (select_engine): the tiled form's windows first, the exhaustive
+    // Fourier search in the same run when they exceed kAutoPruneBudget of tp_full_pairs
+    bool auto_prune = false;
+    uint64_t tp_full_pairs = 0; // block × tile pairs with every window open (Σ groups: blocks · bucket tiles)
+    uint64_t tp_seed_pairs = 0; // block × tile pairs of the seed search (Σ groups: blocks)
     DBuf<int32_t> d_tp_rbk;
     DBuf<uint8_t> d_tp_tmp;
     size_t tp_tmp_bytes = 0;
@@ -423,7 +434,8 @@ int check_params(const frac_params* p, std::string& msg)
         msg = "unknown engine";
         return FRAC_E_INVALID;
     }
-    if (p->flags & ~(FRAC_FLAG_TIMING | FRAC_FLAG_DIRECT_FORM | FRAC_FLAG_SEA_PER_RANGE | FRAC_FLAG_DECODE_STEPWISE)) {
+    if (p->flags & ~(FRAC_FLAG_TIMING | FRAC_FLAG_DIRECT_FORM | FRAC_FLAG_SEA_PER_RANGE | FRAC_FLAG_DECODE_STEPWISE |
+                     FRAC_FLAG_EXHAUSTIVE | FRAC_FLAG_PRUNE)) {
         msg = "unknown flag bits";
         return FRAC_E_INVALID;
     }

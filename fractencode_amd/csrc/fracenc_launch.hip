@@ -309,8 +309,9 @@ void launch_search_dft(frac_ctx* c, const DftArgs& da, unsigned nwg, bool hits)
 }
 
 // n = 8, T = 4: the C4-Fourier search (6 MFMAs per 32×32 tile pair instead of 16).  inits: reset
-// best_key and fb_count in the preparation kernel (launch_all skipped its memsets)
-inline int launch_dft(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool inits)
+// best_key and fb_count in the preparation kernel (launch_all skipped its memsets).  mark_prep = false: the
+// fallback of AUTO's pruned route, whose prep boundary launch_tp marked (this prep counts as search time)
+inline int launch_dft(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool inits, bool mark_prep = true)
 {
     const uint32_t nr = (uint32_t)nranges(c);
     MfmaDomainPrepArgs d;
@@ -387,7 +388,7 @@ inline int launch_dft(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool i
         else
             dft_prep<4><<<grid, 256, 0, c->stream>>>(d, b, c->d_dft_tguard.ptr, trmax, r, c->d_dft_rguard.ptr, in);
     }
-    if (c->p.flags & FRAC_FLAG_TIMING)
+    if ((c->p.flags & FRAC_FLAG_TIMING) && mark_prep)
         FRAC_TRY(mark_event(c, 1));
     const bool four = dft_four_wave(var);
     const std::vector<uint4>& work = four ? c->m_work : c->m8_work;
@@ -686,7 +687,10 @@ int launch_mfma(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool inits =
 // SEA engine, tiled form (fracenc_tp.hip): sorted tiles and blocks, per-range seed bounds,
 // per-group windows, the Fourier search over the windows with per-chunk entries, resolve_dft.
 // One host synchronisation sizes the entry arrays (their count depends on the windows).
-int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing)
+// budgeted (FRAC_ENGINE_AUTO's pruned route): when the windows hold more than kAutoPruneBudget of the run's
+// block × tile pairs the attempt is abandoned before any entry array is sized from them, and the exhaustive
+// Fourier search (launch_dft) produces the records in the same run on the same stream.
+int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, bool budgeted = false)
 {
     const uint32_t nr = (uint32_t)nranges(c), P = c->npos;
     const uint32_t nt = c->ntiles, nbk = c->nblocks, ng = (uint32_t)c->tp_groups.size();
@@ -708,12 +712,12 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing)
     }
     if (nt) {
         tp_build_tiles<<<(nt * 32 + 255) / 256, 256, 0, c->stream>>>(
-            c->tp_bk, c->d_sea_dkey2.ptr, c->d_sea_dpos2.ptr, nt, c->d_m_tile_pos.ptr, c->d_tp_tile_sd.ptr,
+            c->tp_bk, c->d_sea_dkey2.ptr, c->d_sea_dpos2.ptr, nt, c->d_tp_tile_pos.ptr, c->d_tp_tile_sd.ptr,
             c->d_tp_row_of.ptr, c->d_m_dtiles.ptr, c->d_m_dconst.ptr, c->d_dft_tguard.ptr, kTpKS);
         MfmaDomainPrepArgs d;
         d.pool = c->d_pool.ptr;
         d.negsd2 = c->d_negsd2.ptr;
-        d.tile_pos = c->d_m_tile_pos.ptr;
+        d.tile_pos = c->d_tp_tile_pos.ptr;
         d.ntiles = nt;
         d.dtiles = c->d_m_dtiles.ptr;
         d.dconst = c->d_m_dconst.ptr;
@@ -739,14 +743,14 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing)
     }
     if (nbk) {
         tp_build_slots<<<(nbk * 32 + 255) / 256, 256, 0, c->stream>>>(c->tp_bk, c->d_sea_rkey2.ptr, c->d_sea_rord2.ptr,
-                                                                      nbk, c->d_m_slot_range.ptr,
-                                                                      c->d_m_range_slot.ptr, c->d_tp_blk_sr.ptr,
+                                                                      nbk, c->d_tp_slot_range.ptr,
+                                                                      c->d_tp_range_slot.ptr, c->d_tp_blk_sr.ptr,
                                                                       c->d_tp_blk_u.ptr);
         MfmaRangePrepArgs r;
         r.tgt = dtgt;
         r.tstride = tstride;
         r.ranges = c->d_ranges.ptr;
-        r.slot_range = c->d_m_slot_range.ptr;
+        r.slot_range = c->d_tp_slot_range.ptr;
         r.nblocks = nbk;
         r.T = 4;
         r.rfrags = c->d_m_rfrags.ptr;
@@ -757,23 +761,26 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing)
     }
     if (timing)
         FRAC_TRY(mark_event(c, 1));
-    if (!nr || !ng) // no ranges, or no domain in any range's bucket: every record is the default
+    if (!nr || !ng) { // no ranges, or no domain in any range's bucket: every record is the default
+        if (timing && budgeted)
+            FRAC_TRY(mark_event(c, 2));
         return FRAC_OK;
+    }
     constexpr uint32_t W8 = kDftBlocksPerWG;
     DftArgs da;
-    da.m = search_args(c, c->d_m8_work.ptr, ng); // (host-planned only: no plan)
+    da.m = search_args(c, c->d_tp_work.ptr, ng); // (host-planned only: no plan)
     da.rguard = c->d_dft_rguard.ptr;
     da.tguard = c->d_dft_tguard.ptr;
     da.trmax = nullptr; // kTpVar runs the exact epilogue only
     // seed: the Fourier search over one tile per group, one chunk entry per wave (choff = group)
     tp_seed_work<<<(ng + 255) / 256, 256, 0, c->stream>>>(c->d_tp_groups.ptr, ng, c->d_tp_blk_sr.ptr,
-                                                          c->d_tp_tile_sd.ptr, c->d_m8_work.ptr);
+                                                          c->d_tp_tile_sd.ptr, c->d_tp_work.ptr);
     FRAC_HIP(c, c->d_m_entries.ensure((size_t)ng * W8 * 64));
     da.m.entries = c->d_m_entries.ptr;
     da.choff = c->d_tp_iota.ptr;
     search_dft<false, kTpVar, W8, 4, true><<<ng, 64 * W8, 0, c->stream>>>(da);
     tp_seed_reduce<<<(nbk * 32 + 255) / 256, 256, 0, c->stream>>>(c->d_tp_blk_group.ptr, c->d_m_entries.ptr,
-                                                                   c->d_m_slot_range.ptr, c->d_m_rconst.ptr, nbk,
+                                                                   c->d_tp_slot_range.ptr, c->d_m_rconst.ptr, nbk,
                                                                    c->d_tp_blk_u.ptr);
     TpWindowArgs w;
     w.groups = c->d_tp_groups.ptr;
@@ -782,11 +789,12 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing)
     w.blk_u = c->d_tp_blk_u.ptr;
     w.tile_sd = c->d_tp_tile_sd.ptr;
     w.hitH = c->hitH;
-    w.work = c->d_m8_work.ptr;
+    w.work = c->d_tp_work.ptr;
     w.nchunks = c->d_tp_nch.ptr;
     w.pairs = c->d_tp_pairs.ptr;
     w.bk = c->tp_bk;
     w.evals = c->d_tp_evals.ptr;
+    w.sevals = c->d_tp_sevals.ptr;
     FRAC_HIP(c, hipMemsetAsync(c->d_tp_nch.ptr + ng, 0, sizeof(uint32_t), c->stream));
     tp_windows<<<(ng + 255) / 256, 256, 0, c->stream>>>(w);
     size_t tb = c->tp_tmp_bytes;
@@ -796,31 +804,51 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing)
     tp_block_counts<<<(nbk + 255) / 256, 256, 0, c->stream>>>(c->d_tp_blk_group.ptr, c->d_tp_nch.ptr, nbk,
                                                               c->d_tp_blkcnt.ptr);
     tb = c->tp_tmp_bytes;
-    FRAC_HIP(c, hipcub::DeviceScan::ExclusiveSum(c->d_tp_tmp.ptr, tb, c->d_tp_blkcnt.ptr, c->d_m8_blk_ptr.ptr,
+    FRAC_HIP(c, hipcub::DeviceScan::ExclusiveSum(c->d_tp_tmp.ptr, tb, c->d_tp_blkcnt.ptr, c->d_tp_blk_ptr.ptr,
                                                  (int)(nbk + 1), c->stream));
     // sizes of the entry arrays (total chunks, block → entry links) and the searched pairs: one copy
-    tp_totals<<<1, 256, 0, c->stream>>>(c->d_tp_choff.ptr, ng, c->d_m8_blk_ptr.ptr, nbk, c->d_tp_pairs.ptr,
-                                        c->d_tp_evals.ptr, c->d_tp_tot.ptr);
-    uint32_t tot[6] = {0, 0, 0, 0, 0, 0};
+    tp_totals<<<1, 256, 0, c->stream>>>(c->d_tp_choff.ptr, ng, c->d_tp_blk_ptr.ptr, nbk, c->d_tp_pairs.ptr,
+                                        c->d_tp_evals.ptr, c->d_tp_sevals.ptr, c->d_tp_tot.ptr);
+    uint32_t tot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     FRAC_HIP(c, hipMemcpyAsync(tot, c->d_tp_tot.ptr, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
     FRAC_HIP(c, hipStreamSynchronize(c->stream));
+    const uint64_t pairs = (uint64_t)tot[2] | ((uint64_t)tot[3] << 32);
+    if (budgeted) {
+        // the seed search is issued work on either route: one tile per block, the tiled form's MFMAs
+        const uint64_t seed_flops = c->tp_seed_pairs * (kDftTpForm == 6 ? 6ull : 8ull) * 32768ull;
+        const uint64_t seed_evals = (uint64_t)tot[6] | ((uint64_t)tot[7] << 32);
+        if (pairs * kAutoPruneBudgetDen > c->tp_full_pairs * kAutoPruneBudgetNum) {
+            if (getenv("FRAC_TRACE"))
+                fprintf(stderr, "[frac auto] windows %llu of %llu block x tile pairs: over the budget, exhaustive search "
+                                "(no entry array sized)\n", (unsigned long long)pairs, (unsigned long long)c->tp_full_pairs);
+            // launch_dft reads the MFMA route's own maps and lists and rebuilds every frame-derived buffer in
+            // dft_prep (fill_tp); best_key and fb_count were reset by launch_all and nothing has written them
+            FRAC_TRY(launch_dft(c, dtgt, tstride, false, false));
+            c->flops_ran += seed_flops;
+            c->evaluated_ran = c->eligible_pairs + seed_evals;
+            return FRAC_OK;
+        }
+        c->flops_ran = seed_flops;
+        c->evaluated_ran = seed_evals;
+    }
     FRAC_HIP(c, c->d_m_entries.ensure((size_t)tot[0] * kDftBlocksPerWG * 64));
-    FRAC_HIP(c, c->d_m8_blk_ent.ensure(tot[1]));
+    FRAC_HIP(c, c->d_tp_blk_ent.ensure(tot[1]));
     tp_fill_entries<<<(nbk + 255) / 256, 256, 0, c->stream>>>(c->d_tp_blk_group.ptr, c->d_tp_choff.ptr,
-                                                              c->d_m8_blk_ptr.ptr, nbk, c->d_m8_blk_ent.ptr);
+                                                              c->d_tp_blk_ptr.ptr, nbk, c->d_tp_blk_ent.ptr);
     // issued matrix work (8 MFMA 32×32×16 per block × tile) and the (range, domain) pairs in the windows
     // (padding slots and rows of partial blocks and tiles are no pairs)
-    const uint64_t pairs = (uint64_t)tot[2] | ((uint64_t)tot[3] << 32);
-    c->flops_ran = pairs * (kDftTpForm == 6 ? 6ull : 8ull) * 32768ull;
-    c->evaluated_ran = (uint64_t)tot[4] | ((uint64_t)tot[5] << 32);
+    c->flops_ran += pairs * (kDftTpForm == 6 ? 6ull : 8ull) * 32768ull;
+    c->evaluated_ran += (uint64_t)tot[4] | ((uint64_t)tot[5] << 32);
     da.m.entries = c->d_m_entries.ptr;
     da.choff = c->d_tp_choff.ptr;
     launch_search_dft<kTpVar, W8, 4, true>(c, da, ng, c->hitH > 0);
     if (timing)
         FRAC_TRY(mark_event(c, 2));
-    MfmaResolveArgs v = resolve_args(c, dtgt, tstride, nr, c->d_m8_blk_ptr.ptr, c->d_m8_blk_ent.ptr);
+    MfmaResolveArgs v = resolve_args(c, dtgt, tstride, nr, c->d_tp_blk_ptr.ptr, c->d_tp_blk_ent.ptr);
     v.T = 4;
-    v.slot_range = c->d_m_slot_range.ptr;
+    v.slot_range = c->d_tp_slot_range.ptr;
+    v.range_slot = c->d_tp_range_slot.ptr; // (resolve_args names the MFMA route's maps)
+    v.tile_pos = c->d_tp_tile_pos.ptr;
     v.nslots = c->nblocks * 32u;
     v.tpool = c->d_dft_tpool.ptr;
     v.rorb = c->d_dft_rorb.ptr;
@@ -1007,8 +1035,10 @@ int launch_all(frac_ctx* c)
     c->fit_rstat = false;
     c->fit_fused = false;
     const bool use_mfma = c->engine == FRAC_ENGINE_MFMA && !c->all_fallback;
+    // AUTO's pruned route: the tiled form's windows, or the Fourier search after them (launch_tp budgeted)
+    const bool prune = N == 8 && use_mfma && c->auto_prune && !c->qplan;
     // the Fourier path resets best_key and fb_count in its preparation kernel (dft_prep)
-    const bool dft_inits = N == 8 && use_mfma && nr && dft_route(c);
+    const bool dft_inits = N == 8 && use_mfma && nr && dft_route(c) && !prune;
     if (!dft_inits && !c->qplan) { // (a planned level's qt_fill_maps did both)
         if (nr)
             FRAC_HIP(c, hipMemsetAsync(c->d_best_key.ptr, 0xff, nr * sizeof(unsigned long long), c->stream));
@@ -1034,7 +1064,9 @@ int launch_all(frac_ctx* c)
     }
     const bool use_sea = c->engine == FRAC_ENGINE_SEA && !c->all_fallback;
     tr.mark("memsets + pool");
-    if (use_mfma)
+    if (prune)
+        FRAC_TRY(launch_tp(c, dtgt, tstride, timing, true));
+    else if (use_mfma)
         FRAC_TRY(launch_mfma<N>(c, dtgt, tstride, dft_inits));
     if constexpr (N <= 8) {
         if (use_sea)
@@ -1118,7 +1150,7 @@ int launch_all(frac_ctx* c)
     FRAC_HIP(c, hipGetLastError());
     tr.mark("fit + fallback");
     c->engine_ran = use_mfma ? FRAC_ENGINE_MFMA : use_sea ? FRAC_ENGINE_SEA : FRAC_ENGINE_VALU;
-    if (!(use_sea && c->tp)) // the tiled form counted its evaluated pairs in launch_tp
+    if (!(use_sea && c->tp) && !prune) // the tiled form counted its evaluated pairs in launch_tp
         c->evaluated_ran = c->all_fallback ? 0 : c->eligible_pairs; // SEA: read back at fetch
     if (use_valu) {
         c->form_ran = FRAC_FORM_DOT2;

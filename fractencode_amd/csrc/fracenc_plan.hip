@@ -112,6 +112,21 @@ inline bool dft_four_wave(int var)
 // 6 (kDft6, variants 21, 23)
 constexpr int kTpVar = 1 | kDftChain | (kDftTpForm == 6 ? kDft6 : 0); // the SEA tiled form's search_dft
 constexpr uint32_t kTpKS = kDftTpForm == 4 ? 4u : 5u;                    // its domain fragments per tile
+// FRAC_ENGINE_AUTO's pruned route (n = 8, T = 4, ratio 2; DESIGN §4.4, measured in §7.4).
+// kAutoPruneMinPairs: the fewest block × tile pairs (every window open) at which AUTO tries the bound; below
+// it the route's fixed cost — two radix sorts, about ten small launches, one host turnaround — is too large a
+// share of the run to risk on unknown data (FRAC_FLAG_PRUNE ignores it).
+// kAutoPruneBudget: the share of those pairs the windows may hold; above it the windowed search with its exact
+// epilogue and per-chunk entries costs what the exhaustive search does, and the run falls back to that.  It
+// caps the entry arrays too: 128 bytes per pair of a full group, so at most the budget's share of the
+// worst case.
+// Measured (tools/auto_prune_sweep.py, profiles/r08/auto_prune/): a run forced to fall back costs 0.25 – 0.40 ms
+// more than the exhaustive one end to end — 13.5 % at 8.4 M pairs, 8.4 % at 16.7 M (4096², a quarter of the
+// ranges), 3.2 % at 66.9 M — so the 10 % line lies between the first two and the minimum sits just under the
+// smallest size measured within it; the windowed search with its resolve equals the exhaustive search's time at
+// a share of 0.43, rounded down to 3/8.
+constexpr uint64_t kAutoPruneMinPairs = 16000000;
+constexpr uint64_t kAutoPruneBudgetNum = 3, kAutoPruneBudgetDen = 8;
 inline int dft_form(int var)
 {
     if (var == 20 || var == 22)
@@ -420,6 +435,13 @@ void select_engine(frac_ctx* c, const PrepBuckets& B)
         c->tp = c->engine == FRAC_ENGINE_SEA && !c->virt && n == 8 && T == 4 &&
                 !(c->p.flags & FRAC_FLAG_SEA_PER_RANGE) && (st ? atoi(st) != 0 : true);
     }
+    // AUTO, n = 8, T = 4, ratio 2 on the Fourier path: the tiled form's windows first (launch_tp budgeted).
+    // The size condition follows in prepare(), from the groups.  More buckets than the tiled form holds,
+    // a quadtree level (device-planned, or its ranges built on the device) and every other geometry stay
+    // on the exhaustive route as they were.
+    c->auto_prune = c->p.engine == FRAC_ENGINE_AUTO && c->engine == FRAC_ENGINE_MFMA && !c->virt && n == 8 && T == 4 &&
+                    !c->all_fallback && !c->qplan && !c->ranges_dev && mfma_dft_enabled(c) &&
+                    !(c->p.flags & FRAC_FLAG_EXHAUSTIVE) && nb <= kTpMaxBuckets;
 }
 
 // the tiled SEA form's buckets and groups
@@ -453,6 +475,7 @@ int plan_tp_groups(frac_ctx* c, const PrepBuckets& B)
     while ((1u << (c->tp_key_bits - 16)) < (uint32_t)nb)
         ++c->tp_key_bits;
     c->tp_groups.clear();
+    c->tp_full_pairs = c->tp_seed_pairs = 0;
     c->tp_blk_group.assign(nbk, make_uint2(0xffffffffu, 0u));
     for (int b = 0; b < nb; ++b) {
         if (!bk.tile_count[b])
@@ -461,6 +484,8 @@ int plan_tp_groups(frac_ctx* c, const PrepBuckets& B)
             const uint32_t gi = (uint32_t)c->tp_groups.size();
             const uint32_t nbl = std::min(kDftBlocksPerWG, bk.blk_count[b] - g0);
             c->tp_groups.push_back(make_uint4(bk.blk_first[b] + g0, nbl, bk.tile_first[b], bk.tile_count[b]));
+            c->tp_full_pairs += (uint64_t)nbl * bk.tile_count[b];
+            c->tp_seed_pairs += nbl;
             for (uint32_t k = 0; k < nbl; ++k)
                 c->tp_blk_group[bk.blk_first[b] + g0 + k] = make_uint2(gi, k);
         }
@@ -688,9 +713,11 @@ int fill_sea(frac_ctx* c, const PrepBuckets& B)
     FRAC_HIP(c, c->d_sea_dkey2.ensure(P));
     FRAC_HIP(c, c->d_sea_dpos.ensure(P));
     FRAC_HIP(c, c->d_sea_dpos2.ensure(P));
-    FRAC_HIP(c, c->d_sea_ent.ensure(P));
-    FRAC_HIP(c, c->d_sea_snegsd2.ensure(P));
-    FRAC_HIP(c, c->d_sea_spool.ensure(P * (size_t)(n * n / 2)));
+    if (!c->auto_prune) { // (the per-range form's sorted pool: AUTO's pruned route is the tiled form only)
+        FRAC_HIP(c, c->d_sea_ent.ensure(P));
+        FRAC_HIP(c, c->d_sea_snegsd2.ensure(P));
+        FRAC_HIP(c, c->d_sea_spool.ensure(P * (size_t)(n * n / 2)));
+    }
     FRAC_HIP(c, c->d_sea_rkey.ensure(nr));
     FRAC_HIP(c, c->d_sea_rkey2.ensure(nr));
     FRAC_HIP(c, c->d_sea_rord.ensure(nr));
@@ -716,9 +743,21 @@ int fill_tp(frac_ctx* c, const PrepBuckets& B)
 {
     const size_t P = (size_t)c->npos * B.VT, nr = nranges(c);
     const size_t ng = c->tp_groups.size(), nbk = c->nblocks, nt = c->ntiles;
-    FRAC_HIP(c, c->d_m_slot_range.ensure(nbk * 32));
-    FRAC_HIP(c, c->d_m_range_slot.ensure(nr));
-    FRAC_HIP(c, c->d_m_tile_pos.ensure(nt * 32));
+    // The tiled form's layout is ΣD4-sorted tiles and ΣR-sorted blocks, rebuilt every run; the MFMA route's is
+    // the domain and range order, filled once (fill_mfma).  Under AUTO both stay prepared, so per buffer:
+    //   own copy per layout — the maps and lists the MFMA route fills at prepare() and never again: tile_pos,
+    //     slot_range / range_slot, the 8-block work list and its block → entry CSR map (d_tp_* here, d_m_* /
+    //     d_m8_* there).  Small: 4 bytes per tile row, slot, range and entry link.
+    //   shared, rebuilt by whichever search runs — everything a run derives from the frame: the tile fragments
+    //     and constants (d_m_dtiles, d_m_dconst), the guards, the tile-order pool copy (d_dft_tpool), the range
+    //     fragments, constants and orbit copies (d_m_rfrags, d_m_rconst, d_dft_rorb) and d_m_entries.  dft_prep
+    //     writes every row of each, padding rows included, from its own maps (the exhaustive route needs that
+    //     frame after frame anyway), so a fallback reads nothing the abandoned attempt laid out.  The pool and
+    //     −ΣD4² are indexed by pool position in both layouts (dft_domain_build<BYPOS> scatters to row_of only
+    //     the tile-order outputs).
+    FRAC_HIP(c, c->d_tp_slot_range.ensure(nbk * 32));
+    FRAC_HIP(c, c->d_tp_range_slot.ensure(nr));
+    FRAC_HIP(c, c->d_tp_tile_pos.ensure(nt * 32));
     FRAC_HIP(c, c->d_m_dtiles.ensure(nt * kTpKS * 64));
     FRAC_HIP(c, c->d_m_dconst.ensure((size_t)nt * kDftCS * 4 + 256)); // Fourier layout + one DMA piece of slack
     FRAC_HIP(c, c->d_m_rfrags.ensure(nbk * 7 * 64));
@@ -726,8 +765,9 @@ int fill_tp(frac_ctx* c, const PrepBuckets& B)
     FRAC_HIP(c, c->d_dft_tguard.ensure(nt));
     FRAC_HIP(c, c->d_dft_tpool.ensure(nt * 32 * 32));
     FRAC_HIP(c, c->d_dft_rguard.ensure(nbk));
-    FRAC_HIP(c, c->d_m8_work.ensure(ng));
-    FRAC_HIP(c, c->d_m8_blk_ptr.ensure(nbk + 1));
+    FRAC_HIP(c, c->d_tp_work.ensure(ng));
+    FRAC_HIP(c, c->d_tp_blk_ptr.ensure(nbk + 1));
+    FRAC_HIP(c, c->d_tp_sevals.ensure(ng));
     FRAC_HIP(c, c->d_tp_tile_sd.ensure(nt));
     FRAC_HIP(c, c->d_tp_row_of.ensure(P));
     FRAC_HIP(c, c->d_tp_blk_sr.ensure(nbk));
@@ -735,7 +775,7 @@ int fill_tp(frac_ctx* c, const PrepBuckets& B)
     FRAC_HIP(c, c->d_tp_nch.ensure(ng + 1));
     FRAC_HIP(c, c->d_tp_choff.ensure(ng + 1));
     FRAC_HIP(c, c->d_tp_blkcnt.ensure(nbk + 1));
-    FRAC_HIP(c, c->d_tp_tot.ensure(6));
+    FRAC_HIP(c, c->d_tp_tot.ensure(8));
     FRAC_HIP(c, c->d_tp_pairs.ensure(ng));
     FRAC_HIP(c, c->d_tp_evals.ensure(ng));
     FRAC_HIP(c, c->d_tp_rbk.ensure(nr));
@@ -751,7 +791,7 @@ int fill_tp(frac_ctx* c, const PrepBuckets& B)
     size_t s1 = 0, s2 = 0;
     FRAC_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, s1, c->d_tp_nch.ptr, c->d_tp_choff.ptr, (int)(ng + 1),
                                                  c->stream));
-    FRAC_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, s2, c->d_tp_blkcnt.ptr, c->d_m8_blk_ptr.ptr,
+    FRAC_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, s2, c->d_tp_blkcnt.ptr, c->d_tp_blk_ptr.ptr,
                                                  (int)(nbk + 1), c->stream));
     c->tp_tmp_bytes = std::max<size_t>(std::max(s1, s2), 1);
     FRAC_HIP(c, c->d_tp_tmp.ensure(c->tp_tmp_bytes));
@@ -807,16 +847,19 @@ int prepare(frac_ctx* c)
     plan_valu_work(c, B);
     tr.mark("buckets + valu work");
     select_engine(c, B);
-    if (c->tp)
-        FRAC_TRY(plan_tp_groups(c, B));
+    if (c->tp || c->auto_prune)
+        FRAC_TRY(plan_tp_groups(c, B)); // (blocks and tiles per bucket as plan_mfma_work counts them)
+    // AUTO prunes from kAutoPruneMinPairs block × tile pairs up (FRAC_FLAG_PRUNE: whenever there is a pair)
+    if (c->auto_prune)
+        c->auto_prune = c->tp_full_pairs >= ((c->p.flags & FRAC_FLAG_PRUNE) ? 1ull : kAutoPruneMinPairs);
     c->dft_copies = 1;
     if (c->engine == FRAC_ENGINE_MFMA)
         FRAC_TRY(plan_mfma_work(c, B));
     tr.mark("engine work");
     FRAC_TRY(fill_common(c, B));
-    if (c->engine == FRAC_ENGINE_SEA)
+    if (c->engine == FRAC_ENGINE_SEA || c->auto_prune)
         FRAC_TRY(fill_sea(c, B));
-    if (c->tp)
+    if (c->tp || c->auto_prune)
         FRAC_TRY(fill_tp(c, B));
     if (c->engine == FRAC_ENGINE_MFMA)
         FRAC_TRY(fill_mfma(c));

@@ -159,6 +159,7 @@ int qt_encode_dev(frac_ctx* c, const frac_quadtree_params* qp, LevelGrid& level,
         c->npos = nd;
         c->engine = FRAC_ENGINE_MFMA;
         c->tp = false;
+        c->auto_prune = false; // a planned level stays on the exhaustive route
         c->hitH = compute_hit_limit(c->p.rms_threshold, 4 * n * n);
         c->all_fallback = false;
         const bool fourier = n == 8 && mfma_dft_enabled(c);

@@ -223,6 +223,7 @@ struct TpWindowArgs {
     uint32_t* pairs;      // [ngroups] block × tile pairs searched (frac_stats.matrix_flops)
     TpBuckets bk;
     unsigned long long* evals; // [ngroups] (range, domain) pairs in the window (frac_stats.evaluated_mappings)
+    unsigned long long* sevals; // [ngroups] (range, domain) pairs of the seed tile, read from work (tp_seed_work)
 };
 
 __global__ void __launch_bounds__(256) tp_windows(TpWindowArgs a)
@@ -231,6 +232,7 @@ __global__ void __launch_bounds__(256) tp_windows(TpWindowArgs a)
     if (gi >= a.ngroups)
         return;
     const uint4 gr = a.groups[gi];
+    const uint32_t seed = a.work[gi].z; // the seed search's tile, before the window replaces it
     uint32_t srlo = 0xffffffffu, srhi = 0, u = 0;
     for (uint32_t k = 0; k < gr.y; ++k) {
         const uint2 s = a.blk_sr[gr.x + k];
@@ -273,34 +275,44 @@ __global__ void __launch_bounds__(256) tp_windows(TpWindowArgs a)
     const uint32_t slots = min(gr.y * 32u, a.bk.rng_count[b] - (gr.x - a.bk.blk_first[b]) * 32u);
     const uint32_t r0 = (t0 - gr.z) * 32u, r1 = min((t1 - gr.z) * 32u, a.bk.dom_count[b]);
     a.evals[gi] = (unsigned long long)slots * (r1 > r0 ? r1 - r0 : 0u);
+    const uint32_t s0 = (seed - gr.z) * 32u;
+    a.sevals[gi] = (unsigned long long)slots * (min(s0 + 32u, a.bk.dom_count[b]) - s0);
 }
 
-// the totals the host needs in one 24-byte copy: {chunks, block → entry links, Σ pairs (u64), Σ evals (u64)}
+// the totals the host needs in one 32-byte copy: {chunks, block → entry links, Σ pairs (u64), Σ evals (u64),
+// Σ seed evals (u64)}
 __global__ void __launch_bounds__(256) tp_totals(const uint32_t* __restrict__ choff, uint32_t ngroups,
                                                  const uint32_t* __restrict__ blk_ptr, uint32_t nblocks,
                                                  const uint32_t* __restrict__ pairs,
                                                  const unsigned long long* __restrict__ evals,
+                                                 const unsigned long long* __restrict__ sevals,
                                                  uint32_t* __restrict__ tot)
 {
-    __shared__ unsigned long long part[2][4];
-    unsigned long long s = 0, v = 0;
+    __shared__ unsigned long long part[3][4];
+    unsigned long long s = 0, v = 0, q = 0;
     for (uint32_t g = threadIdx.x; g < ngroups; g += blockDim.x) {
         s += pairs[g];
         v += evals[g];
+        q += sevals[g];
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         s += __shfl_xor(s, o, 64);
         v += __shfl_xor(v, o, 64);
+        q += __shfl_xor(q, o, 64);
     }
     if ((threadIdx.x & 63u) == 0) {
         part[0][threadIdx.x >> 6] = s;
         part[1][threadIdx.x >> 6] = v;
+        part[2][threadIdx.x >> 6] = q;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         const unsigned long long t = part[0][0] + part[0][1] + part[0][2] + part[0][3];
         const unsigned long long e = part[1][0] + part[1][1] + part[1][2] + part[1][3];
+        const unsigned long long se = part[2][0] + part[2][1] + part[2][2] + part[2][3];
+        tot[6] = (uint32_t)se;
+        tot[7] = (uint32_t)(se >> 32);
         tot[0] = choff[ngroups];
         tot[1] = blk_ptr[nblocks];
         tot[2] = (uint32_t)t;

@@ -42,7 +42,10 @@ extern "C" {
 #define FRAC_E_NOMEM (-4)       /* device or host allocation failed                      */
 
 /* engines (frac_params.engine) */
-#define FRAC_ENGINE_AUTO 0      /* fastest engine that supports the geometry             */
+#define FRAC_ENGINE_AUTO 0      /* fastest engine that supports the geometry.  n = 8, T = 4, ratio 2 on a  */
+                                /* large enough run: the MFMA search pruned by the exact elimination bound  */
+                                /* (the tiled SEA form's windows), falling back to the exhaustive Fourier   */
+                                /* search in the same run when the windows are not small; same records      */
 #define FRAC_ENGINE_VALU 1      /* v_dot2_u32_u16 scalar-broadcast search                */
 #define FRAC_ENGINE_MFMA 2      /* f16 MFMA search with an exact integer epilogue        */
 #define FRAC_ENGINE_SEA 3       /* successive elimination: exact per-candidate bound skips   */
@@ -57,6 +60,11 @@ extern "C" {
                                     /* instead of the rotation-group Fourier form                               */
 #define FRAC_FLAG_SEA_PER_RANGE 4u  /* SEA engine, n = 8, T = 4: the per-range form instead of the tiled one   */
 #define FRAC_FLAG_DECODE_STEPWISE 8u /* decoder: one apply + one rms launch per iteration (no fused loop)       */
+/* FRAC_ENGINE_AUTO's pruned route (n = 8, T = 4, ratio 2; added after ABI 9 without changing FRAC_ABI_VERSION:
+ * an older library refuses them as unknown flag bits).  Neither changes a record; an explicit engine ignores both. */
+#define FRAC_FLAG_EXHAUSTIVE 16u    /* AUTO never prunes: a run time that does not depend on the frame's content */
+#define FRAC_FLAG_PRUNE 32u         /* AUTO prunes whenever the geometry allows it, however small the run        */
+                                    /* (FRAC_FLAG_EXHAUSTIVE wins when both are set)                             */
 
 /* == Frac2::UniformGridItem (image/partition2.hpp:93-99): GridItemBase{origin, size}
  *    + GridItemData{bb_classifierBin}; 20 bytes. category -1 = not classified
@@ -122,7 +130,8 @@ typedef struct frac_stats {
 #define FRAC_FORM_DIRECT 1  /* MFMA engine: one f16 GEMM per transform (n²·T MACs per pair)        */
 #define FRAC_FORM_FOURIER 2 /* MFMA engine, n = 8, T = 4: rotation-group Fourier form (96 MACs)    */
 #define FRAC_FORM_SEA 3     /* SEA engine: bound-pruned exact evaluation (v_dot2)                */
-#define FRAC_FORM_SEA_MFMA 4 /* SEA engine, n = 8, T = 4: the bound per tile pair, Fourier MFMA search */
+#define FRAC_FORM_SEA_MFMA 4 /* SEA engine, and AUTO's pruned route (engine = MFMA), n = 8, T = 4: the bound */
+                             /* per tile pair, Fourier MFMA search over the surviving windows              */
 #define FRAC_FORM_SAMPLED 5 /* range sizes outside {2,4,8,16}: per range an exact integer scan of the */
                             /* pool rows, one per (domain, transform), sampled as RootMeanSquare does  */
 
@@ -173,7 +182,10 @@ int frac_set_domains(frac_ctx* ctx, const frac_grid_item* domains, size_t nd);
 int frac_set_ranges(frac_ctx* ctx, const frac_grid_item* ranges, size_t nr);
 
 /* Launch the whole search for the current planes/grids on the context's stream
- * (asynchronous).  frac_fetch waits for it and copies results/stats to the host. */
+ * (asynchronous).  frac_fetch waits for it and copies results/stats to the host.
+ * On FRAC_ENGINE_AUTO's pruned route (and on FRAC_ENGINE_SEA's tiled form) frac_run blocks the host once,
+ * mid-run: it waits for the window sizes (one 32-byte copy) before it sizes and launches the search over
+ * them, or the exhaustive search when they exceed the budget.  The rest of the run is asynchronous as ever. */
 int frac_run(frac_ctx* ctx);
 int frac_fetch(frac_ctx* ctx, frac_encode_item* out, frac_stats* stats);
 int frac_sync(frac_ctx* ctx);

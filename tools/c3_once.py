@@ -4,7 +4,9 @@
 Mode "e2e" runs bench.py's headline step instead: per rep the frame H2D from pinned memory, the
 search and the 32-byte tuples D2H into pinned memory (bench.FrameStep at N = 1), so a kernel trace
 of it times search_dft under the headline's own conditions (roofline.kernel_ms).
-usage: tools/c3_once.py [mfma|sea|valu] [reps] [e2e]"""
+"auto" is FRAC_ENGINE_AUTO, which at this size takes the pruned route (the tiled form's windows under the MFMA
+engine).
+usage: tools/c3_once.py [mfma|auto|sea|valu] [reps] [e2e]"""
 import os
 import sys
 
@@ -13,7 +15,7 @@ sys.path.insert(0, ROOT)
 import fractencode_amd as F  # noqa: E402
 from fractencode_amd.synth import value_noise  # noqa: E402
 
-eng = {"mfma": F.ENGINE_MFMA, "sea": F.ENGINE_SEA, "valu": F.ENGINE_VALU}[sys.argv[1] if len(sys.argv) > 1 else "mfma"]
+eng = {"mfma": F.ENGINE_MFMA, "auto": F.ENGINE_AUTO, "sea": F.ENGINE_SEA, "valu": F.ENGINE_VALU}[sys.argv[1] if len(sys.argv) > 1 else "mfma"]
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 2
 e2e = len(sys.argv) > 3 and sys.argv[3] == "e2e"
 S = 4096
