@@ -108,6 +108,10 @@ struct frac_ctx {
     // the streams come before every buffer: members go in reverse order, the buffers first
     Stream own_stream;
     hipStream_t stream = nullptr; // own_stream, or the caller's (frac_set_stream)
+    // the tiled form's range sort runs here, beside the domain sort on `stream` (launch_tp: forked after tp_keys,
+    // joined before tp_build in the same call, so nothing of a run is left on it when launch_tp returns its
+    // stream to the caller); created on the first tiled run
+    Stream tp_aux_stream;
     // frac_set_frame_async (ABI 9): the frame after the current one is uploaded into d_src_next on copy_stream
     // while the context's stream still reads d_src; the two swap at the call (created on first use).
     // Frame streaming from host memory: the upload runs on the context's copy stream into the plane buffer the
@@ -230,7 +234,11 @@ struct frac_ctx {
     std::vector<uint2> tp_blk_group;
     DBuf<uint4> d_tp_groups;
     DBuf<uint2> d_tp_blk_group, d_tp_tile_sd, d_tp_blk_sr;
-    DBuf<uint32_t> d_tp_blk_u, d_tp_nch, d_tp_choff, d_tp_blkcnt, d_tp_tot, d_tp_iota, d_tp_pairs, d_tp_row_of;
+    DBuf<uint32_t> d_tp_blk_u, d_tp_nch, d_tp_choff, d_tp_iota, d_tp_pairs, d_tp_row_of;
+    struct TpTotals {
+        uint32_t w[8];
+    };
+    Pinned<TpTotals> h_tp_tot; // mapped: tp_plan writes the run's totals there (read after launch_tp's synchronisation)
     // the tiled form's own maps and work lists, in its sorted layout (rebuilt every run): under AUTO the
     // MFMA engine's domain-ordered ones (d_m_tile_pos, the slot maps, d_m8_*) stay prepared beside them
     DBuf<int32_t> d_tp_slot_range, d_tp_tile_pos;
@@ -243,8 +251,8 @@ struct frac_ctx {
     uint64_t tp_full_pairs = 0; // block × tile pairs with every window open (Σ groups: blocks · bucket tiles)
     uint64_t tp_seed_pairs = 0; // block × tile pairs of the seed search (Σ groups: blocks)
     DBuf<int32_t> d_tp_rbk;
-    DBuf<uint8_t> d_tp_tmp;
-    size_t tp_tmp_bytes = 0;
+    DBuf<uint8_t> d_tp_sort_tmp; // the range sort's own scratch (sea_tmp_bytes): the two sorts run at the same time
+    Event tp_fork, tp_join;
     DBuf<Frc1MinMax> d_frc_mm;             // frac_pack_frc1
     DBuf<unsigned long long> d_frc_rec;
     DBuf<uint32_t> d_frc_words;
@@ -301,6 +309,8 @@ struct frac_ctx {
             (void)hipStreamSynchronize(stream);
         if (frame.copy_stream)
             (void)hipStreamSynchronize(frame.copy_stream);
+        if (tp_aux_stream)
+            (void)hipStreamSynchronize(tp_aux_stream);
     }
 
     int fail(int code, const std::string& msg)

@@ -223,7 +223,7 @@ struct DftDomainBuildArgs {
     uint32_t* pool;             // [P][32] packed u16 pairs of D4
     int32_t* negsd2;            // [P]
     uint32_t* tpool;            // [ntiles*32][32] the same rows in tile order, orbit order (resolve_dft)
-    const uint32_t* row_of = nullptr; // BYPOS: [P] tile row of each pool position (tp_build_tiles)
+    const uint32_t* row_of = nullptr; // BYPOS: [P] tile row of each pool position (tp_build)
     uint32_t npos = 0;                // BYPOS: P
 };
 
@@ -231,7 +231,7 @@ struct DftDomainBuildArgs {
 
 // BYPOS (the SEA tiled form, whose tiles hold domains in ΣD4 order): one thread per pool
 // position in domain order, so neighbouring threads read overlapping plane rows, and the
-// outputs are scattered to the position's tile row; tp_build_tiles writes the padding rows and
+// outputs are scattered to the position's tile row; tp_build writes the padding rows and
 // zeroes the tile guards, which are then raised with atomics.
 // F5: the five-MFMA form's fragments [s_b + u_b | s_b − u_b | γ | γ − δ | −δ − γ] (kDft5)
 template <bool BYPOS = false, bool F5 = false>
@@ -376,20 +376,24 @@ __device__ __forceinline__ void dft_domain_build_at(uint32_t tid, const MfmaDoma
 // guard terms meet in a lane-pair shuffle.  On a small frame the single-thread chain per row ran one
 // wave per CU on a quarter of the CUs (C2: 16 workgroups); this halves the chain and doubles the waves.
 // A tile's 32 rows are one wave's 64 lanes, so the tile guards stay a wave reduction.
+// BYPOS (the SEA tiled form, as dft_domain_build_at's): the lane pair takes a pool position in domain order and
+// scatters the tile-order outputs to its row (row_of); a tile's rows are then in many waves, so the guards are
+// raised with atomics over the zeroes tp_build wrote (no padding row comes here, and no trmax).
 constexpr uint32_t kDbRowWords = 33; // LDS words per row: 32 + 1 of padding (rows in distinct banks)
-template <bool F5>
+template <bool F5, bool BYPOS = false>
 __device__ __forceinline__ void dft_domain_build_pair_at(uint32_t tid2, const MfmaDomainPrepArgs& a,
                                                          const DftDomainBuildArgs& s, uint2* __restrict__ tguard,
                                                          int32_t* __restrict__ trmax)
 {
     constexpr int KS = F5 ? 5 : 4;
     __shared__ uint32_t rows[128 * kDbRowWords]; // 256 threads = 128 rows
-    const uint32_t gid = tid2 >> 1, hh = tid2 & 1u;
-    if (gid >= a.ntiles * 32u) // whole tiles (whole waves) leave together
+    const uint32_t hh = tid2 & 1u;
+    if ((tid2 >> 1) >= (BYPOS ? s.npos : a.ntiles * 32u)) // whole tiles (whole waves; BYPOS: lane pairs) leave together
         return;
+    const uint32_t gid = BYPOS ? s.row_of[tid2 >> 1] : tid2 >> 1;
     const uint32_t tile = gid >> 5, row = gid & 31u;
     uint32_t* lrow = rows + ((threadIdx.x >> 1) & 127u) * kDbRowWords;
-    const int p = a.tile_pos[gid];
+    const int p = BYPOS ? (int)(tid2 >> 1) : a.tile_pos[gid];
     uint32_t w[16]; // words 16hh … 16hh + 15 of the row: D4 rows 4hh … 4hh + 3, two cells per word
     int sq = 0;
     if (p >= 0) {
@@ -490,6 +494,13 @@ __device__ __forceinline__ void dft_domain_build_pair_at(uint32_t tid2, const Mf
         a.dconst[(size_t)tile * (kDftCS * 4) + h * 16 + i] = __float_as_uint(ny);
     }
     uint32_t gx = p >= 0 ? (uint32_t)((F5 ? 2 : 4) * dinf) : 0u, gy = p >= 0 ? (uint32_t)sb2 : 0u;
+    if constexpr (BYPOS) {
+        if (hh == 0) {
+            atomicMax(&tguard[tile].x, gx);
+            atomicMax(&tguard[tile].y, gy);
+        }
+        return;
+    }
     // the tile's guard terms over its 32 rows (lanes 2·row + hh of one wave): a wave maximum
 #pragma unroll
     for (int o = 32; o > 1; o >>= 1) {

@@ -687,6 +687,8 @@ int launch_mfma(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool inits =
 // SEA engine, tiled form (fracenc_tp.hip): sorted tiles and blocks, per-range seed bounds,
 // per-group windows, the Fourier search over the windows with per-chunk entries, resolve_dft.
 // One host synchronisation sizes the entry arrays (their count depends on the windows).
+// Outside the two sorts the route is ten commands: tp_keys (with the run's resets), tp_build, tp_prep, the seed
+// search_dft, tp_seed_windows, tp_plan, the synchronisation, tp_fill_entries, search_dft and resolve_dft.
 // budgeted (FRAC_ENGINE_AUTO's pruned route): when the windows hold more than kAutoPruneBudget of the run's
 // block × tile pairs the attempt is abandoned before any entry array is sized from them, and the exhaustive
 // Fourier search (launch_dft) produces the records in the same run on the same stream.
@@ -701,19 +703,93 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
     c->form_ran = FRAC_FORM_SEA_MFMA;
     c->flops_ran = 0;
     c->evaluated_ran = 0;
-    if (P) {
-        tp_domain_keys<<<(P + 255) / 256, 256, 0, c->stream>>>(c->d_src.ptr, c->d_sstride, c->d_doms.ptr,
-                                                               c->d_porig.ptr, P, c->d_sea_bend.ptr,
-                                                               (uint32_t)c->bucket_end.size(), c->d_sea_dkey.ptr,
-                                                               c->d_sea_dpos.ptr);
-        size_t tb = c->sea_tmp_bytes;
-        FRAC_HIP(c, sort_pairs_u32(c->d_sea_tmp.ptr, tb, c->d_sea_dkey.ptr, c->d_sea_dkey2.ptr, c->d_sea_dpos.ptr,
-                                   c->d_sea_dpos2.ptr, P, c->tp_key_bits, c->stream));
+    // both sides' sort keys, and the run's best_key and fb_count resets (launch_all skipped its fills)
+    if (P || nr) {
+        TpKeyArgs k;
+        k.src = c->d_src.ptr;
+        k.sstride = c->d_sstride;
+        k.doms = c->d_doms.ptr;
+        k.porig = c->d_porig.ptr;
+        k.P = P;
+        k.bucket_end = c->d_sea_bend.ptr;
+        k.nb = (uint32_t)c->bucket_end.size();
+        k.dkey = c->d_sea_dkey.ptr;
+        k.dpos = c->d_sea_dpos.ptr;
+        k.dblocks = (P + 255) / 256;
+        k.tgt = dtgt;
+        k.tstride = tstride;
+        k.ranges = c->d_ranges.ptr;
+        k.rbucket_idx = c->d_tp_rbk.ptr;
+        k.nr = nr;
+        k.rkey = c->d_sea_rkey.ptr;
+        k.rord = c->d_sea_rord.ptr;
+        k.best_key = c->d_best_key.ptr;
+        k.fb_count = c->d_fb_count.ptr;
+        tp_keys<<<k.dblocks + (nr + 255) / 256, 256, 0, c->stream>>>(k);
     }
-    if (nt) {
-        tp_build_tiles<<<(nt * 32 + 255) / 256, 256, 0, c->stream>>>(
-            c->tp_bk, c->d_sea_dkey2.ptr, c->d_sea_dpos2.ptr, nt, c->d_tp_tile_pos.ptr, c->d_tp_tile_sd.ptr,
-            c->d_tp_row_of.ptr, c->d_m_dtiles.ptr, c->d_m_dconst.ptr, c->d_dft_tguard.ptr, kTpKS);
+    // The two sorts do not depend on each other, and a pass over so few items is bound by its look-back chain,
+    // not by bandwidth: the range sort goes to the context's auxiliary stream, with scratch of its own, forked
+    // after tp_keys (so after everything this stream waited for: an upload, the previous run) and joined before
+    // tp_build.  Nothing returns between the fork and the join's wait, whatever failed in between.
+    hipError_t rsort = hipSuccess, dsort = hipSuccess, join = hipSuccess;
+    if (nr && P) {
+        if (!c->tp_aux_stream) {
+            FRAC_HIP(c, hipStreamCreateWithFlags(&c->tp_aux_stream.s, hipStreamNonBlocking));
+            FRAC_HIP(c, hipEventCreateWithFlags(&c->tp_fork.e, hipEventDisableTiming));
+            FRAC_HIP(c, hipEventCreateWithFlags(&c->tp_join.e, hipEventDisableTiming));
+        }
+        FRAC_HIP(c, hipEventRecord(c->tp_fork, c->stream));
+        FRAC_HIP(c, hipStreamWaitEvent(c->tp_aux_stream, c->tp_fork, 0));
+        size_t tb = c->sea_tmp_bytes;
+        rsort = sort_pairs_u32(c->d_tp_sort_tmp.ptr, tb, c->d_sea_rkey.ptr, c->d_sea_rkey2.ptr, c->d_sea_rord.ptr,
+                               c->d_sea_rord2.ptr, nr, c->tp_key_bits, c->tp_aux_stream);
+        join = hipEventRecord(c->tp_join, c->tp_aux_stream);
+    } else if (nr) {
+        size_t tb = c->sea_tmp_bytes;
+        rsort = sort_pairs_u32(c->d_sea_tmp.ptr, tb, c->d_sea_rkey.ptr, c->d_sea_rkey2.ptr, c->d_sea_rord.ptr,
+                               c->d_sea_rord2.ptr, nr, c->tp_key_bits, c->stream);
+    }
+    if (P) {
+        size_t tb = c->sea_tmp_bytes;
+        dsort = sort_pairs_u32(c->d_sea_tmp.ptr, tb, c->d_sea_dkey.ptr, c->d_sea_dkey2.ptr, c->d_sea_dpos.ptr,
+                               c->d_sea_dpos2.ptr, P, c->tp_key_bits, c->stream);
+    }
+    if (nr && P) {
+        if (join == hipSuccess)
+            join = hipStreamWaitEvent(c->stream, c->tp_join, 0);
+        if (join != hipSuccess) // no event, or no wait on it: the host waits for the auxiliary stream itself
+            (void)hipStreamSynchronize(c->tp_aux_stream);
+    }
+    FRAC_HIP(c, rsort);
+    FRAC_HIP(c, dsort);
+    FRAC_HIP(c, join);
+    // the tiles and the slots from the two sorted orders
+    if (nt || nbk) {
+        TpBuildArgs t;
+        t.bk = c->tp_bk;
+        t.skey = c->d_sea_dkey2.ptr;
+        t.spos = c->d_sea_dpos2.ptr;
+        t.ntiles = nt;
+        t.tile_pos = c->d_tp_tile_pos.ptr;
+        t.tile_sd = c->d_tp_tile_sd.ptr;
+        t.row_of = c->d_tp_row_of.ptr;
+        t.dtiles = c->d_m_dtiles.ptr;
+        t.dconst = c->d_m_dconst.ptr;
+        t.tguard = c->d_dft_tguard.ptr;
+        t.ks = kTpKS;
+        t.tblocks = (nt * 32 + 255) / 256;
+        t.rkey = c->d_sea_rkey2.ptr;
+        t.rord = c->d_sea_rord2.ptr;
+        t.nblocks = nbk;
+        t.slot_range = c->d_tp_slot_range.ptr;
+        t.range_slot = c->d_tp_range_slot.ptr;
+        t.blk_sr = c->d_tp_blk_sr.ptr;
+        t.blk_u = c->d_tp_blk_u.ptr;
+        tp_build<<<t.tblocks + (nbk * 32 + 255) / 256, 256, 0, c->stream>>>(t);
+    }
+    // the domain tiles by pool position, the range blocks, and the seed work (which reads what tp_build wrote)
+    const bool search = nr && ng; // else no ranges, or no domain in any range's bucket
+    {
         MfmaDomainPrepArgs d;
         d.pool = c->d_pool.ptr;
         d.negsd2 = c->d_negsd2.ptr;
@@ -731,21 +807,6 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
         b.tpool = c->d_dft_tpool.ptr;
         b.row_of = c->d_tp_row_of.ptr;
         b.npos = P;
-        if (P)
-            dft_domain_build<true, kDftTpForm != 4><<<(P + 255) / 256, 256, 0, c->stream>>>(d, b, c->d_dft_tguard.ptr);
-    }
-    if (nr) {
-        tp_range_keys<<<(nr + 255) / 256, 256, 0, c->stream>>>(dtgt, tstride, c->d_ranges.ptr, c->d_tp_rbk.ptr, nr,
-                                                               c->d_sea_rkey.ptr, c->d_sea_rord.ptr);
-        size_t tb = c->sea_tmp_bytes;
-        FRAC_HIP(c, sort_pairs_u32(c->d_sea_tmp.ptr, tb, c->d_sea_rkey.ptr, c->d_sea_rkey2.ptr, c->d_sea_rord.ptr,
-                                   c->d_sea_rord2.ptr, nr, c->tp_key_bits, c->stream));
-    }
-    if (nbk) {
-        tp_build_slots<<<(nbk * 32 + 255) / 256, 256, 0, c->stream>>>(c->tp_bk, c->d_sea_rkey2.ptr, c->d_sea_rord2.ptr,
-                                                                      nbk, c->d_tp_slot_range.ptr,
-                                                                      c->d_tp_range_slot.ptr, c->d_tp_blk_sr.ptr,
-                                                                      c->d_tp_blk_u.ptr);
         MfmaRangePrepArgs r;
         r.tgt = dtgt;
         r.tstride = tstride;
@@ -755,13 +816,26 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
         r.T = 4;
         r.rfrags = c->d_m_rfrags.ptr;
         r.rconst = c->d_m_rconst.ptr;
-        FRAC_HIP(c, c->d_dft_rorb.ensure((size_t)r.nblocks * 32 * 32));
+        FRAC_HIP(c, c->d_dft_rorb.ensure((size_t)std::max(nbk, 1u) * 32 * 32));
         r.rorb = c->d_dft_rorb.ptr;
-        dft_range_prep<kDftTpForm><<<(nbk * 32 + 255) / 256, 256, 0, c->stream>>>(r, c->d_dft_rguard.ptr);
+        TpSeedWorkArgs sw;
+        if (search) {
+            sw.groups = c->d_tp_groups.ptr;
+            sw.ngroups = ng;
+            sw.blk_sr = c->d_tp_blk_sr.ptr;
+            sw.tile_sd = c->d_tp_tile_sd.ptr;
+            sw.work = c->d_tp_work.ptr;
+        }
+        const uint64_t dthreads = (uint64_t)P * (kTpPairBuild ? 2 : 1); // lanes per pool position
+        const uint32_t dblocks = nt && P ? (uint32_t)((dthreads + 255) / 256) : 0u;
+        const uint32_t rblocks = (nbk * 64 + 255) / 256; // two lanes per range slot
+        const uint32_t pg = dblocks + rblocks + (sw.ngroups + 255) / 256;
+        if (pg)
+            tp_prep<<<pg, 256, 0, c->stream>>>(d, b, c->d_dft_tguard.ptr, dblocks, r, c->d_dft_rguard.ptr, rblocks, sw);
     }
     if (timing)
         FRAC_TRY(mark_event(c, 1));
-    if (!nr || !ng) { // no ranges, or no domain in any range's bucket: every record is the default
+    if (!search) { // every record is the default
         if (timing && budgeted)
             FRAC_TRY(mark_event(c, 2));
         return FRAC_OK;
@@ -773,20 +847,19 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
     da.tguard = c->d_dft_tguard.ptr;
     da.trmax = nullptr; // kTpVar runs the exact epilogue only
     // seed: the Fourier search over one tile per group, one chunk entry per wave (choff = group)
-    tp_seed_work<<<(ng + 255) / 256, 256, 0, c->stream>>>(c->d_tp_groups.ptr, ng, c->d_tp_blk_sr.ptr,
-                                                          c->d_tp_tile_sd.ptr, c->d_tp_work.ptr);
     FRAC_HIP(c, c->d_m_entries.ensure((size_t)ng * W8 * 64));
     da.m.entries = c->d_m_entries.ptr;
     da.choff = c->d_tp_iota.ptr;
     search_dft<false, kTpVar, W8, 4, true><<<ng, 64 * W8, 0, c->stream>>>(da);
-    tp_seed_reduce<<<(nbk * 32 + 255) / 256, 256, 0, c->stream>>>(c->d_tp_blk_group.ptr, c->d_m_entries.ptr,
-                                                                   c->d_tp_slot_range.ptr, c->d_m_rconst.ptr, nbk,
-                                                                   c->d_tp_blk_u.ptr);
+    // per group: its blocks' seed bounds, then its window
     TpWindowArgs w;
     w.groups = c->d_tp_groups.ptr;
     w.ngroups = ng;
     w.blk_sr = c->d_tp_blk_sr.ptr;
     w.blk_u = c->d_tp_blk_u.ptr;
+    w.entries = c->d_m_entries.ptr;
+    w.slot_range = c->d_tp_slot_range.ptr;
+    w.rconst = c->d_m_rconst.ptr;
     w.tile_sd = c->d_tp_tile_sd.ptr;
     w.hitH = c->hitH;
     w.work = c->d_tp_work.ptr;
@@ -795,23 +868,18 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
     w.bk = c->tp_bk;
     w.evals = c->d_tp_evals.ptr;
     w.sevals = c->d_tp_sevals.ptr;
-    FRAC_HIP(c, hipMemsetAsync(c->d_tp_nch.ptr + ng, 0, sizeof(uint32_t), c->stream));
-    tp_windows<<<(ng + 255) / 256, 256, 0, c->stream>>>(w);
-    size_t tb = c->tp_tmp_bytes;
-    FRAC_HIP(c, hipcub::DeviceScan::ExclusiveSum(c->d_tp_tmp.ptr, tb, c->d_tp_nch.ptr, c->d_tp_choff.ptr, (int)(ng + 1),
-                                                 c->stream));
-    FRAC_HIP(c, hipMemsetAsync(c->d_tp_blkcnt.ptr + nbk, 0, sizeof(uint32_t), c->stream));
-    tp_block_counts<<<(nbk + 255) / 256, 256, 0, c->stream>>>(c->d_tp_blk_group.ptr, c->d_tp_nch.ptr, nbk,
-                                                              c->d_tp_blkcnt.ptr);
-    tb = c->tp_tmp_bytes;
-    FRAC_HIP(c, hipcub::DeviceScan::ExclusiveSum(c->d_tp_tmp.ptr, tb, c->d_tp_blkcnt.ptr, c->d_tp_blk_ptr.ptr,
-                                                 (int)(nbk + 1), c->stream));
-    // sizes of the entry arrays (total chunks, block → entry links) and the searched pairs: one copy
-    tp_totals<<<1, 256, 0, c->stream>>>(c->d_tp_choff.ptr, ng, c->d_tp_blk_ptr.ptr, nbk, c->d_tp_pairs.ptr,
-                                        c->d_tp_evals.ptr, c->d_tp_sevals.ptr, c->d_tp_tot.ptr);
-    uint32_t tot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    FRAC_HIP(c, hipMemcpyAsync(tot, c->d_tp_tot.ptr, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
+    tp_seed_windows<<<ng, 256, 0, c->stream>>>(w);
+    // the chunk and entry offsets, and the totals (sizes of the entry arrays, the searched pairs) written
+    // straight into the host's pinned block
+    void* dtot = nullptr;
+    FRAC_HIP(c, hipHostGetDevicePointer(&dtot, c->h_tp_tot.ptr, 0));
+    tp_plan<<<1, kTpPlanThreads, 0, c->stream>>>(c->d_tp_nch.ptr, ng, c->d_tp_blk_group.ptr, nbk, c->d_tp_pairs.ptr,
+                                                 c->d_tp_evals.ptr, c->d_tp_sevals.ptr, c->d_tp_choff.ptr,
+                                                 c->d_tp_blk_ptr.ptr, reinterpret_cast<uint32_t*>(dtot));
     FRAC_HIP(c, hipStreamSynchronize(c->stream));
+    uint32_t tot[8];
+    for (int k = 0; k < 8; ++k)
+        tot[k] = c->h_tp_tot->w[k];
     const uint64_t pairs = (uint64_t)tot[2] | ((uint64_t)tot[3] << 32);
     if (budgeted) {
         // the seed search is issued work on either route: one tile per block, the tiled form's MFMAs
@@ -822,7 +890,7 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
                 fprintf(stderr, "[frac auto] windows %llu of %llu block x tile pairs: over the budget, exhaustive search "
                                 "(no entry array sized)\n", (unsigned long long)pairs, (unsigned long long)c->tp_full_pairs);
             // launch_dft reads the MFMA route's own maps and lists and rebuilds every frame-derived buffer in
-            // dft_prep (fill_tp); best_key and fb_count were reset by launch_all and nothing has written them
+            // dft_prep (fill_tp); best_key and fb_count were reset by tp_keys and nothing has written them
             FRAC_TRY(launch_dft(c, dtgt, tstride, false, false));
             c->flops_ran += seed_flops;
             c->evaluated_ran = c->eligible_pairs + seed_evals;
@@ -1039,7 +1107,9 @@ int launch_all(frac_ctx* c)
     const bool prune = N == 8 && use_mfma && c->auto_prune && !c->qplan;
     // the Fourier path resets best_key and fb_count in its preparation kernel (dft_prep)
     const bool dft_inits = N == 8 && use_mfma && nr && dft_route(c) && !prune;
-    if (!dft_inits && !c->qplan) { // (a planned level's qt_fill_maps did both)
+    // so does the tiled form, in its key kernel (tp_keys: launch_tp, by either caller)
+    const bool tp_inits = N == 8 && nr && (prune || (c->engine == FRAC_ENGINE_SEA && !c->all_fallback && c->tp));
+    if (!dft_inits && !tp_inits && !c->qplan) { // (a planned level's qt_fill_maps did both)
         if (nr)
             FRAC_HIP(c, hipMemsetAsync(c->d_best_key.ptr, 0xff, nr * sizeof(unsigned long long), c->stream));
         const uint32_t fbc = c->all_fallback ? nr : 0u;

@@ -738,7 +738,7 @@ int fill_sea(frac_ctx* c, const PrepBuckets& B)
     return FRAC_OK;
 }
 
-// the tiled SEA form's buffers, groups and scan scratch
+// the tiled SEA form's buffers and groups
 int fill_tp(frac_ctx* c, const PrepBuckets& B)
 {
     const size_t P = (size_t)c->npos * B.VT, nr = nranges(c);
@@ -774,8 +774,8 @@ int fill_tp(frac_ctx* c, const PrepBuckets& B)
     FRAC_HIP(c, c->d_tp_blk_u.ensure(nbk));
     FRAC_HIP(c, c->d_tp_nch.ensure(ng + 1));
     FRAC_HIP(c, c->d_tp_choff.ensure(ng + 1));
-    FRAC_HIP(c, c->d_tp_blkcnt.ensure(nbk + 1));
-    FRAC_HIP(c, c->d_tp_tot.ensure(8));
+    FRAC_HIP(c, c->h_tp_tot.ensure());
+    FRAC_HIP(c, c->d_tp_sort_tmp.ensure(c->sea_tmp_bytes)); // (fill_sea ran: the larger of the sorts' needs)
     FRAC_HIP(c, c->d_tp_pairs.ensure(ng));
     FRAC_HIP(c, c->d_tp_evals.ensure(ng));
     FRAC_HIP(c, c->d_tp_rbk.ensure(nr));
@@ -788,13 +788,6 @@ int fill_tp(frac_ctx* c, const PrepBuckets& B)
     for (size_t g = 0; g < ng; ++g)
         c->tp_iota[g] = (uint32_t)g;
     FRAC_TRY(upload(c, c->d_tp_iota, c->tp_iota));
-    size_t s1 = 0, s2 = 0;
-    FRAC_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, s1, c->d_tp_nch.ptr, c->d_tp_choff.ptr, (int)(ng + 1),
-                                                 c->stream));
-    FRAC_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, s2, c->d_tp_blkcnt.ptr, c->d_tp_blk_ptr.ptr,
-                                                 (int)(nbk + 1), c->stream));
-    c->tp_tmp_bytes = std::max<size_t>(std::max(s1, s2), 1);
-    FRAC_HIP(c, c->d_tp_tmp.ensure(c->tp_tmp_bytes));
     return FRAC_OK;
 }
 

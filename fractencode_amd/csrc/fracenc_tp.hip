@@ -6,9 +6,9 @@
 //     tile with its [min, max] ΣD4; ranges of each bucket sorted by ΣR into 32-range blocks,
 //     groups of 8 blocks per workgroup as in the exhaustive search;
 //   * seed: the Fourier search over one tile per group (the tile nearest its middle block's
-//     ΣR), tp_seed_reduce turning each range's maximum into U_r, the least exact error over
+//     ΣR), tp_seed_windows turning each range's maximum into U_r, the least exact error over
 //     that tile (any real candidate's error bounds the range's minimum from above);
-//   * tp_windows: per group the tiles whose ΣD4 interval meets [min ΣR − D, max ΣR + D],
+//   * then, in the same launch: per group the tiles whose ΣD4 interval meets [min ΣR − D, max ΣR + D],
 //     D² = n²·(max(U, H) + 1/2) over the group's ranges: outside it (ΣR − ΣD)²/n² alone
 //     exceeds the bound, so no candidate there can win, tie or hit (fracenc_sea.hip);
 //   * search_dft<…, CHUNKED> over each group's window, one entry per 4-tile chunk (the tiles
@@ -21,6 +21,9 @@
 namespace fracenc {
 
 constexpr int kTpMaxBuckets = 8;
+// tp_prep's domain half: two lanes per pool position (dft_domain_build_pair_at, BYPOS), or one
+// (dft_domain_build_at); DESIGN §7.4 has the two times
+constexpr bool kTpPairBuild = true;
 
 struct TpBuckets {
     uint32_t nb;
@@ -31,12 +34,11 @@ struct TpBuckets {
 };
 
 // range sort key: (bucket << 16) | ΣR (ΣR = 4Σr ≤ 65280 < 2^16)
-__global__ void __launch_bounds__(256) tp_range_keys(const uint8_t* __restrict__ tgt, uint32_t tstride,
-                                                     const frac_grid_item* __restrict__ ranges,
-                                                     const int32_t* __restrict__ rbucket_idx, uint32_t nr,
-                                                     uint32_t* __restrict__ key, uint32_t* __restrict__ idx)
+__device__ __forceinline__ void tp_range_keys_at(uint32_t r, const uint8_t* __restrict__ tgt, uint32_t tstride,
+                                                 const frac_grid_item* __restrict__ ranges,
+                                                 const int32_t* __restrict__ rbucket_idx, uint32_t nr,
+                                                 uint32_t* __restrict__ key, uint32_t* __restrict__ idx)
 {
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= nr)
         return;
     const frac_grid_item rg = ranges[r];
@@ -57,13 +59,12 @@ __device__ inline uint32_t byte_sum4(uint32_t w)
     return (t & 0xffffu) + (t >> 16);
 }
 
-__global__ void __launch_bounds__(256) tp_domain_keys(const uint8_t* __restrict__ src, uint32_t sstride,
-                                                      const frac_grid_item* __restrict__ doms,
-                                                      const uint32_t* __restrict__ porig, uint32_t P,
-                                                      const uint32_t* __restrict__ bucket_end, uint32_t nb,
-                                                      uint32_t* __restrict__ key, uint32_t* __restrict__ pos)
+__device__ __forceinline__ void tp_domain_keys_at(uint32_t p, const uint8_t* __restrict__ src, uint32_t sstride,
+                                                  const frac_grid_item* __restrict__ doms,
+                                                  const uint32_t* __restrict__ porig, uint32_t P,
+                                                  const uint32_t* __restrict__ bucket_end, uint32_t nb,
+                                                  uint32_t* __restrict__ key, uint32_t* __restrict__ pos)
 {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= P)
         return;
     const frac_grid_item d = doms[porig[p]];
@@ -89,17 +90,56 @@ __global__ void __launch_bounds__(256) tp_domain_keys(const uint8_t* __restrict_
     pos[p] = p;
 }
 
+// tp_keys: both sides' sort keys and the run's resets in one launch, as dft_prep arranges them.  Blocks
+// [0, dblocks) take the domains, the rest the ranges; every thread also takes a grid-stride share of the
+// best_key reset, and thread 0 clears the fallback count (launch_all leaves both to this kernel).
+struct TpKeyArgs {
+    const uint8_t* src;
+    uint32_t sstride;
+    const frac_grid_item* doms;
+    const uint32_t* porig;
+    uint32_t P;
+    const uint32_t* bucket_end;
+    uint32_t nb;
+    uint32_t* dkey;
+    uint32_t* dpos;
+    uint32_t dblocks; // blocks of the domain half
+    const uint8_t* tgt;
+    uint32_t tstride;
+    const frac_grid_item* ranges;
+    const int32_t* rbucket_idx;
+    uint32_t nr;
+    uint32_t* rkey;
+    uint32_t* rord;
+    unsigned long long* best_key; // nr entries set to ~0 (no candidate yet)
+    uint32_t* fb_count;
+};
+
+__global__ void __launch_bounds__(256) tp_keys(TpKeyArgs a)
+{
+    const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
+    for (uint32_t i = gt; i < a.nr; i += gridDim.x * blockDim.x)
+        a.best_key[i] = ~0ull;
+    if (gt == 0)
+        *a.fb_count = 0u;
+    if (blockIdx.x < a.dblocks)
+        tp_domain_keys_at(gt, a.src, a.sstride, a.doms, a.porig, a.P, a.bucket_end, a.nb, a.dkey, a.dpos);
+    else
+        tp_range_keys_at((blockIdx.x - a.dblocks) * blockDim.x + threadIdx.x, a.tgt, a.tstride, a.ranges,
+                         a.rbucket_idx, a.nr, a.rkey, a.rord);
+}
+
 // tile rows from the sorted domain order; per tile [min, max] ΣD4 of its valid rows; for
 // dft_domain_build<BYPOS>: the tile row of each pool position, the padding rows' fragments
 // (b = 0) and epilogue constants, and zeroed tile guards
-__global__ void __launch_bounds__(256) tp_build_tiles(TpBuckets bk, const uint32_t* __restrict__ skey,
-                                                      const uint32_t* __restrict__ spos, uint32_t ntiles,
-                                                      int32_t* __restrict__ tile_pos, uint2* __restrict__ tile_sd,
-                                                      uint32_t* __restrict__ row_of, uint4* __restrict__ dtiles,
-                                                      uint32_t* __restrict__ dconst, uint2* __restrict__ tguard,
-                                                      uint32_t ks)
+__device__ __forceinline__ void tp_build_tiles_at(uint32_t gid, const TpBuckets& bk,
+                                                  const uint32_t* __restrict__ skey,
+                                                  const uint32_t* __restrict__ spos, uint32_t ntiles,
+                                                  int32_t* __restrict__ tile_pos, uint2* __restrict__ tile_sd,
+                                                  uint32_t* __restrict__ row_of, uint4* __restrict__ dtiles,
+                                                  uint32_t* __restrict__ dconst, uint2* __restrict__ tguard,
+                                                  uint32_t ks)
 {
-    const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= ntiles * 32u)
         return;
     const uint32_t tile = gid >> 5, row = gid & 31u;
@@ -131,13 +171,13 @@ __global__ void __launch_bounds__(256) tp_build_tiles(TpBuckets bk, const uint32
 }
 
 // range slots from the sorted range order; per block [min, max] ΣR of its valid slots
-__global__ void __launch_bounds__(256) tp_build_slots(TpBuckets bk, const uint32_t* __restrict__ rkey,
-                                                      const uint32_t* __restrict__ rord, uint32_t nblocks,
-                                                      int32_t* __restrict__ slot_range,
-                                                      uint32_t* __restrict__ range_slot, uint2* __restrict__ blk_sr,
-                                                      uint32_t* __restrict__ blk_u)
+__device__ __forceinline__ void tp_build_slots_at(uint32_t gid, const TpBuckets& bk,
+                                                  const uint32_t* __restrict__ rkey,
+                                                  const uint32_t* __restrict__ rord, uint32_t nblocks,
+                                                  int32_t* __restrict__ slot_range,
+                                                  uint32_t* __restrict__ range_slot, uint2* __restrict__ blk_sr,
+                                                  uint32_t* __restrict__ blk_u)
 {
-    const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= nblocks * 32u)
         return;
     const uint32_t blk = gid >> 5, col = gid & 31u;
@@ -157,12 +197,44 @@ __global__ void __launch_bounds__(256) tp_build_slots(TpBuckets bk, const uint32
     }
 }
 
-// seed work: per group the one tile of its bucket nearest the ΣR of its middle block
-__global__ void __launch_bounds__(256) tp_seed_work(const uint4* __restrict__ groups, uint32_t ngroups,
-                                                    const uint2* __restrict__ blk_sr, const uint2* __restrict__ tile_sd,
-                                                    uint4* __restrict__ work)
+// tp_build: the tiles and the slots in one launch after both sorts; blocks [0, tblocks) take the tiles
+struct TpBuildArgs {
+    TpBuckets bk;
+    const uint32_t* skey; // sorted domain keys and positions
+    const uint32_t* spos;
+    uint32_t ntiles;
+    int32_t* tile_pos;
+    uint2* tile_sd;
+    uint32_t* row_of;
+    uint4* dtiles;
+    uint32_t* dconst;
+    uint2* tguard;
+    uint32_t ks;
+    uint32_t tblocks;     // blocks of the tile half
+    const uint32_t* rkey; // sorted range keys and indices
+    const uint32_t* rord;
+    uint32_t nblocks;
+    int32_t* slot_range;
+    uint32_t* range_slot;
+    uint2* blk_sr;
+    uint32_t* blk_u;
+};
+
+__global__ void __launch_bounds__(256) tp_build(TpBuildArgs a)
 {
-    const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
+    if (blockIdx.x < a.tblocks)
+        tp_build_tiles_at(blockIdx.x * blockDim.x + threadIdx.x, a.bk, a.skey, a.spos, a.ntiles, a.tile_pos, a.tile_sd,
+                          a.row_of, a.dtiles, a.dconst, a.tguard, a.ks);
+    else
+        tp_build_slots_at((blockIdx.x - a.tblocks) * blockDim.x + threadIdx.x, a.bk, a.rkey, a.rord, a.nblocks,
+                          a.slot_range, a.range_slot, a.blk_sr, a.blk_u);
+}
+
+// seed work: per group the one tile of its bucket nearest the ΣR of its middle block
+__device__ __forceinline__ void tp_seed_work_at(uint32_t gi, const uint4* __restrict__ groups, uint32_t ngroups,
+                                                const uint2* __restrict__ blk_sr, const uint2* __restrict__ tile_sd,
+                                                uint4* __restrict__ work)
+{
     if (gi >= ngroups)
         return;
     const uint4 gr = groups[gi];
@@ -179,35 +251,55 @@ __global__ void __launch_bounds__(256) tp_seed_work(const uint4* __restrict__ gr
     work[gi] = make_uint4(gr.x, gr.y, gr.z + lo, gr.z + lo + 1);
 }
 
+// tp_prep: everything the seed search reads, in one launch after tp_build.  Blocks [0, dblocks) build the domain
+// tiles by pool position (dft_domain_build, BYPOS), the next rblocks the range blocks, two lanes per slot
+// (dft_range_prep_pair_at), and the trailing blocks the seed work, which reads only what tp_build wrote.
+struct TpSeedWorkArgs {
+    const uint4* groups = nullptr;
+    uint32_t ngroups = 0; // 0: no seed work in this launch
+    const uint2* blk_sr = nullptr;
+    const uint2* tile_sd = nullptr;
+    uint4* work = nullptr;
+};
+
+__global__ void __launch_bounds__(256) tp_prep(MfmaDomainPrepArgs d, DftDomainBuildArgs s, uint2* __restrict__ tguard,
+                                               uint32_t dblocks, MfmaRangePrepArgs r, uint32_t* __restrict__ rguard,
+                                               uint32_t rblocks, TpSeedWorkArgs w)
+{
+    if (blockIdx.x < dblocks) {
+        if constexpr (kTpPairBuild)
+            dft_domain_build_pair_at<kDftTpForm != 4, true>(blockIdx.x * blockDim.x + threadIdx.x, d, s, tguard, nullptr);
+        else
+            dft_domain_build_at<true, kDftTpForm != 4>(blockIdx.x * blockDim.x + threadIdx.x, d, s, tguard, nullptr);
+    } else if (blockIdx.x < dblocks + rblocks) {
+        dft_range_prep_pair_at<kDftTpForm>((blockIdx.x - dblocks) * blockDim.x + threadIdx.x, r, rguard);
+    } else {
+        tp_seed_work_at((blockIdx.x - dblocks - rblocks) * blockDim.x + threadIdx.x, w.groups, w.ngroups, w.blk_sr,
+                        w.tile_sd, w.work);
+    }
+}
+
 // per block: the seed search's maximum y over the seed tile gives each slot U = 16Σa² − y, the
 // least exact error over that tile (exact regime; else no bound); the block's bound is the
 // greatest U over its slots (a 32-lane reduction, one writer per block)
-__global__ void __launch_bounds__(256) tp_seed_reduce(const uint2* __restrict__ blk_group,
-                                                      const uint2* __restrict__ entries,
-                                                      const int32_t* __restrict__ slot_range,
-                                                      const uint32_t* __restrict__ rconst, uint32_t nblocks,
-                                                      uint32_t* __restrict__ blk_u)
+// (block `blk` is wave `k` of group `gi`'s seed workgroup; every lane of the 32-lane row returns the bound)
+__device__ __forceinline__ uint32_t tp_seed_reduce_row(uint32_t gi, uint32_t k, uint32_t blk, uint32_t col, bool live,
+                                                       const uint2* __restrict__ entries,
+                                                       const int32_t* __restrict__ slot_range,
+                                                       const uint32_t* __restrict__ rconst)
 {
-    const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= nblocks * 32u) // whole blocks: the 32 lanes of a block leave together
-        return;
-    const uint32_t b = gid >> 5, col = gid & 31u;
-    const uint2 gw = blk_group[b];
-    if (gw.x == 0xffffffffu)
-        return;
     uint32_t u = 0u;
-    if (slot_range[gid] >= 0) {
-        const size_t e = ((size_t)gw.x * 8u + gw.y) * 64u + col;
+    if (live && slot_range[blk * 32u + col] >= 0) {
+        const size_t e = ((size_t)gi * 8u + k) * 64u + col;
         const float y = fmaxf(__uint_as_float(entries[e].x), __uint_as_float(entries[e + 32].x));
-        const int64_t sa16 = (int64_t)rconst[gid];
+        const int64_t sa16 = (int64_t)rconst[blk * 32u + col];
         // y = 16Σa² − min S16 is exact while min S16 < 2^24 (fracenc_dft.hip)
         u = y > (float)(sa16 - kExactLimit) ? (uint32_t)(sa16 - (int64_t)y) : 0xffffffffu;
     }
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1)
         u = max(u, (uint32_t)__shfl_xor((int)u, o, 64));
-    if (col == 0)
-        blk_u[b] = u;
+    return u;
 }
 
 // per group of ≤ 8 blocks: the tile window and its chunk count
@@ -215,7 +307,10 @@ struct TpWindowArgs {
     const uint4* groups;  // [ngroups] {first block, nblocks, tile_first, tile_count} (static)
     uint32_t ngroups;
     const uint2* blk_sr;
-    const uint32_t* blk_u;
+    uint32_t* blk_u;      // [nblocks] the seed bound of each block (written here)
+    const uint2* entries; // the seed search's entries, one chunk per group
+    const int32_t* slot_range;
+    const uint32_t* rconst;
     const uint2* tile_sd;
     int64_t hitH;         // −1: no hits
     uint4* work;          // [ngroups] {first block, nblocks, t0, t1}
@@ -223,22 +318,35 @@ struct TpWindowArgs {
     uint32_t* pairs;      // [ngroups] block × tile pairs searched (frac_stats.matrix_flops)
     TpBuckets bk;
     unsigned long long* evals; // [ngroups] (range, domain) pairs in the window (frac_stats.evaluated_mappings)
-    unsigned long long* sevals; // [ngroups] (range, domain) pairs of the seed tile, read from work (tp_seed_work)
+    unsigned long long* sevals; // [ngroups] (range, domain) pairs of the seed tile, read from work (tp_prep)
 };
 
-__global__ void __launch_bounds__(256) tp_windows(TpWindowArgs a)
+// tp_seed_windows: one workgroup per group.  Each 32-lane row reduces the seed search's entries of one block of
+// the group to its bound (tp_seed_reduce_row) and writes blk_u; one thread then sets the group's window.
+__global__ void __launch_bounds__(256) tp_seed_windows(TpWindowArgs a)
 {
-    const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gi >= a.ngroups)
-        return;
+    __shared__ uint32_t su[kDftBlocksPerWG];
+    const uint32_t gi = blockIdx.x;
     const uint4 gr = a.groups[gi];
+    {
+        const uint32_t k = threadIdx.x >> 5, col = threadIdx.x & 31u;
+        const bool live = k < gr.y;
+        const uint32_t bu = tp_seed_reduce_row(gi, k, gr.x + k, col, live, a.entries, a.slot_range, a.rconst);
+        if (live && col == 0) {
+            a.blk_u[gr.x + k] = bu;
+            su[k] = bu;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x != 0)
+        return;
     const uint32_t seed = a.work[gi].z; // the seed search's tile, before the window replaces it
     uint32_t srlo = 0xffffffffu, srhi = 0, u = 0;
     for (uint32_t k = 0; k < gr.y; ++k) {
         const uint2 s = a.blk_sr[gr.x + k];
         srlo = min(srlo, s.x);
         srhi = max(srhi, s.y);
-        u = max(u, a.blk_u[gr.x + k]);
+        u = max(u, su[k]);
     }
     uint32_t t0 = gr.z, t1 = gr.z + gr.w; // the whole bucket when no bound is known
     if (u != 0xffffffffu && gr.w) {
@@ -279,21 +387,112 @@ __global__ void __launch_bounds__(256) tp_windows(TpWindowArgs a)
     a.sevals[gi] = (unsigned long long)slots * (min(s0 + 32u, a.bk.dom_count[b]) - s0);
 }
 
-// the totals the host needs in one 32-byte copy: {chunks, block → entry links, Σ pairs (u64), Σ evals (u64),
-// Σ seed evals (u64)}
-__global__ void __launch_bounds__(256) tp_totals(const uint32_t* __restrict__ choff, uint32_t ngroups,
-                                                 const uint32_t* __restrict__ blk_ptr, uint32_t nblocks,
-                                                 const uint32_t* __restrict__ pairs,
-                                                 const unsigned long long* __restrict__ evals,
-                                                 const unsigned long long* __restrict__ sevals,
-                                                 uint32_t* __restrict__ tot)
+// tp_plan: the entry arrays' layout and the totals the host needs, in one workgroup that walks its inputs in
+// passes of kTpPlanThreads with a carry:
+//   choff[0..ng]    the exclusive scan of the groups' chunk counts;
+//   blk_ptr[0..nbk] the exclusive scan of each block's entry count, its group's chunk count (none: 0);
+//   tot[0..8)       {chunks, block → entry links, Σ pairs (u64), Σ evals (u64), Σ seed evals (u64)}, written
+//                   straight into the host's pinned block (read after the stream synchronisation).
+constexpr uint32_t kTpPlanThreads = 256;
+
+// A pass alone is a chain of latencies (its loads, six shuffle steps, a barrier): kTpPlanAhead passes are taken
+// together, their loads and their in-wave scans side by side, under one barrier; the carry then runs through
+// their sums in registers.  (Eight measured best on a 4096² frame's 4 + 32 passes: one workgroup runs its code
+// once, from a cold instruction cache, and 32 unrolled passes cost more in code than they save in latency.)
+constexpr uint32_t kTpPlanAhead = 8;
+constexpr uint32_t kTpPlanWaves = kTpPlanThreads / 64;
+
+// the workgroup's exclusive scans of kTpPlanAhead passes, one value per thread and pass (0 past the input):
+// v[j] becomes the thread's offset in pass j, and the carry moves past them.  wsum: per pass one word per wave,
+// two sets taken in turn (`flip`), so one barrier per call is enough: a wave two calls ahead has crossed the
+// barrier that every reader of this set arrives at afterwards
+__device__ __forceinline__ void tp_plan_scan(uint32_t (&v)[kTpPlanAhead], uint32_t& carry,
+                                             uint32_t (*wsum)[kTpPlanAhead][kTpPlanWaves], uint32_t& flip)
 {
-    __shared__ unsigned long long part[3][4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t inc[kTpPlanAhead];
+#pragma unroll
+    for (uint32_t j = 0; j < kTpPlanAhead; ++j)
+        inc[j] = v[j];
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1)
+#pragma unroll
+        for (uint32_t j = 0; j < kTpPlanAhead; ++j) {
+            const uint32_t t = (uint32_t)__shfl_up((int)inc[j], o, 64);
+            if (lane >= (uint32_t)o)
+                inc[j] += t;
+        }
+    uint32_t(*ws)[kTpPlanWaves] = wsum[flip];
+    flip ^= 1u;
+    if (lane == 63u)
+#pragma unroll
+        for (uint32_t j = 0; j < kTpPlanAhead; ++j)
+            ws[j][wave] = inc[j];
+    __syncthreads();
+#pragma unroll
+    for (uint32_t j = 0; j < kTpPlanAhead; ++j) {
+        uint32_t before = 0, total = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < kTpPlanWaves; ++k) {
+            before += k < wave ? ws[j][k] : 0u;
+            total += ws[j][k];
+        }
+        v[j] = carry + before + inc[j] - v[j];
+        carry += total;
+    }
+}
+
+__global__ void __launch_bounds__(kTpPlanThreads) tp_plan(const uint32_t* __restrict__ nchunks, uint32_t ngroups,
+                                                          const uint2* __restrict__ blk_group, uint32_t nblocks,
+                                                          const uint32_t* __restrict__ pairs,
+                                                          const unsigned long long* __restrict__ evals,
+                                                          const unsigned long long* __restrict__ sevals,
+                                                          uint32_t* __restrict__ choff, uint32_t* __restrict__ blk_ptr,
+                                                          uint32_t* __restrict__ tot)
+{
+    __shared__ uint32_t wsum[2][kTpPlanAhead][kTpPlanWaves];
+    __shared__ unsigned long long part[3][kTpPlanThreads / 64];
     unsigned long long s = 0, v = 0, q = 0;
-    for (uint32_t g = threadIdx.x; g < ngroups; g += blockDim.x) {
-        s += pairs[g];
-        v += evals[g];
-        q += sevals[g];
+    uint32_t carry = 0, flip = 0;
+    // (uniform bounds: every thread takes every pass)
+    for (uint32_t g0 = 0; g0 < ngroups; g0 += kTpPlanAhead * kTpPlanThreads) {
+        uint32_t n[kTpPlanAhead];
+#pragma unroll
+        for (uint32_t j = 0; j < kTpPlanAhead; ++j) {
+            const uint32_t g = g0 + j * kTpPlanThreads + threadIdx.x;
+            n[j] = 0u;
+            if (g < ngroups) {
+                n[j] = nchunks[g];
+                s += pairs[g];
+                v += evals[g];
+                q += sevals[g];
+            }
+        }
+        tp_plan_scan(n, carry, wsum, flip);
+#pragma unroll
+        for (uint32_t j = 0; j < kTpPlanAhead; ++j) {
+            const uint32_t g = g0 + j * kTpPlanThreads + threadIdx.x;
+            if (g < ngroups)
+                choff[g] = n[j];
+        }
+    }
+    const uint32_t chunks = carry;
+    carry = 0;
+    for (uint32_t b0 = 0; b0 < nblocks; b0 += kTpPlanAhead * kTpPlanThreads) {
+        uint32_t n[kTpPlanAhead];
+#pragma unroll
+        for (uint32_t j = 0; j < kTpPlanAhead; ++j) {
+            const uint32_t b = b0 + j * kTpPlanThreads + threadIdx.x;
+            const uint32_t gi = b < nblocks ? blk_group[b].x : 0xffffffffu;
+            n[j] = gi == 0xffffffffu ? 0u : nchunks[gi];
+        }
+        tp_plan_scan(n, carry, wsum, flip);
+#pragma unroll
+        for (uint32_t j = 0; j < kTpPlanAhead; ++j) {
+            const uint32_t b = b0 + j * kTpPlanThreads + threadIdx.x;
+            if (b < nblocks)
+                blk_ptr[b] = n[j];
+        }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -308,28 +507,23 @@ __global__ void __launch_bounds__(256) tp_totals(const uint32_t* __restrict__ ch
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const unsigned long long t = part[0][0] + part[0][1] + part[0][2] + part[0][3];
-        const unsigned long long e = part[1][0] + part[1][1] + part[1][2] + part[1][3];
-        const unsigned long long se = part[2][0] + part[2][1] + part[2][2] + part[2][3];
-        tot[6] = (uint32_t)se;
-        tot[7] = (uint32_t)(se >> 32);
-        tot[0] = choff[ngroups];
-        tot[1] = blk_ptr[nblocks];
+        unsigned long long t = 0, e = 0, se = 0;
+        for (uint32_t k = 0; k < kTpPlanThreads / 64; ++k) {
+            t += part[0][k];
+            e += part[1][k];
+            se += part[2][k];
+        }
+        choff[ngroups] = chunks;
+        blk_ptr[nblocks] = carry;
+        tot[0] = chunks;
+        tot[1] = carry;
         tot[2] = (uint32_t)t;
         tot[3] = (uint32_t)(t >> 32);
         tot[4] = (uint32_t)e;
         tot[5] = (uint32_t)(e >> 32);
+        tot[6] = (uint32_t)se;
+        tot[7] = (uint32_t)(se >> 32);
     }
-}
-
-// per block: entry count = its group's chunk count
-__global__ void __launch_bounds__(256) tp_block_counts(const uint2* __restrict__ blk_group,
-                                                       const uint32_t* __restrict__ nchunks, uint32_t nblocks,
-                                                       uint32_t* __restrict__ cnt)
-{
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < nblocks)
-        cnt[b] = blk_group[b].x == 0xffffffffu ? 0u : nchunks[blk_group[b].x];
 }
 
 // CSR block → entry bases ((chunk_offset[group] + c) · 8 + wave) read by resolve_dft
