@@ -404,6 +404,11 @@ int frac_set_tuple_sink(frac_ctx* c, void* dst)
     if (!c)
         return FRAC_E_INVALID;
     c->tuple_sink = static_cast<frac_tuple*>(dst);
+    // where it lies decides the order the sorted resolve writes it in (launch_tp); an address the runtime does
+    // not know counts as device memory
+    hipPointerAttribute_t at{};
+    c->tuple_sink_host = dst && hipPointerGetAttributes(&at, dst) == hipSuccess && at.type == hipMemoryTypeHost;
+    (void)hipGetLastError();
     return FRAC_OK;
 }
 

@@ -225,6 +225,7 @@ struct frac_ctx {
     DBuf<int32_t> d_sea_snegsd2;
     DBuf<frac_tuple> d_tuples; // frac_fetch_tuples staging
     frac_tuple* tuple_sink = nullptr; // frac_set_tuple_sink: every frac_run's tuples also go here
+    bool tuple_sink_host = false;     // the sink is host memory (the sorted resolve then walks in range order)
     // SEA engine, tiled form (fracenc_tp.hip)
     bool tp = false;
     TpBuckets tp_bk{};

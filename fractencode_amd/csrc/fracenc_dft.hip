@@ -1534,13 +1534,13 @@ struct DftResolved {
     uint32_t bx = 0, bs1 = 0, bs2 = 0, sr1 = 0, sr2 = 0;
 };
 
+// ri: the slot's range (slot_range[slot], which the caller holds; < 0: padding)
 template <bool SORTED>
-__device__ inline DftResolved resolve_dft_eval(const MfmaResolveArgs& a, uint32_t slot, int lane, bool flip)
+__device__ inline DftResolved resolve_dft_eval(const MfmaResolveArgs& a, uint32_t slot, int ri, int lane, bool flip)
 {
     constexpr int PG = 16, T = 4; // T: the rotations evaluated per slot
     const uint32_t TK = a.T;      // the transforms of the keys (4, or 8 with the flipped copies)
     DftResolved res;
-    const int ri = a.slot_range[slot];
     // the slot-only loads go out with the padding check's (slot < nslots: in bounds either way)
     const unsigned long long sb = a.slotbest ? a.slotbest[slot] : 0ull;
     const int64_t sa16 = (int64_t)a.rconst[slot];
@@ -1772,10 +1772,10 @@ __device__ inline void resolve_dft_record(const MfmaResolveArgs& a, uint32_t r, 
                                           const frac_grid_item& rg)
 {
     if (a.fused_fit) { // the range's record right here: one launch less per run (C2: 5 µs of a 43 µs frame)
-        if (lane == 0) {
+        // the whole wave: the record and the tuple leave as whole stores (fit_rstat_range_wave)
+        if (lane == 0)
             a.best_key[r] = w.bestk;
-            fit_rstat_range<8>(a.fit, r, w.bestk, make_uint4(w.bx, w.bs1 | (w.sr1 << 16), w.bs2, w.sr2), &rg);
-        }
+        fit_rstat_range_wave<8>(a.fit, r, w.bestk, make_uint4(w.bx, w.bs1 | (w.sr1 << 16), w.bs2, w.sr2), rg, lane);
         return;
     }
     if (lane == 0) {
@@ -1794,9 +1794,10 @@ __device__ inline void resolve_dft_slot(const MfmaResolveArgs& a, uint32_t slot,
     if (ri < 0)
         return;
     const frac_grid_item rg = a.fused_fit ? a.fit.ranges[ri] : frac_grid_item{};
-    DftResolved w = resolve_dft_eval<SORTED>(a, slot, lane, false);
+    DftResolved w = resolve_dft_eval<SORTED>(a, slot, ri, lane, false);
     if (!SORTED && a.flip_slots) {
-        const DftResolved f = resolve_dft_eval<SORTED>(a, slot + a.flip_slots, lane, true);
+        const DftResolved f =
+            resolve_dft_eval<SORTED>(a, slot + a.flip_slots, a.slot_range[slot + a.flip_slots], lane, true);
         if (f.bestk < w.bestk)
             w = f;
     }
@@ -1814,7 +1815,8 @@ __device__ inline void resolve_dft_pair(const MfmaResolveArgs& a, uint32_t slot,
     if (ri < 0)
         return;
     const frac_grid_item rg = (a.fused_fit && wave == 0) ? a.fit.ranges[ri] : frac_grid_item{};
-    const DftResolved w = resolve_dft_eval<false>(a, slot + wave * a.flip_slots, lane, wave == 1);
+    const uint32_t ws = slot + wave * a.flip_slots;
+    const DftResolved w = resolve_dft_eval<false>(a, ws, a.slot_range[ws], lane, wave == 1);
     if (wave == 1 && lane == 0) {
         fkey = w.bestk;
         fsums[0] = w.bx;
@@ -1839,10 +1841,30 @@ __device__ inline void resolve_dft_pair(const MfmaResolveArgs& a, uint32_t slot,
 // One wave per slot, in slot order (the 32 ranges of a block read the same entry lines back to
 // back); launched as one- or four-wave workgroups. A grid of fewer, longer-lived waves striding over the slots measured slower (452 vs
 // 372 µs at C3 in the SEA tiled form).
+//
+// BY_RANGE (the sorted route writing a tuple sink in host memory, launch_tp): one wave per range in range order
+// instead (slot = range_slot[r], padding slots never visited, grid ⌈nr / 4⌉), so neighbouring waves write
+// neighbouring tuples — the four waves of a workgroup 128 contiguous bytes of the sink — as the exhaustive route's
+// slot walk does.  In (bucket, ΣR) order no two tuples written near each other in time share a host line, which cost
+// the C3 finish 0.12 ms across PCIe; the price of range order is that a block's 32 slots no longer read its entry
+// rows back to back, 0.05 ms at C3, so a run without a host sink keeps the slot order.
+// kTpRangeOrder = false keeps the slot order everywhere.
+constexpr bool kTpRangeOrder = true;
 
-template <bool SORTED = false>
+// range r of the sorted route, range order: its slot from the inverse map (tp_build writes one per range)
+__device__ inline void resolve_dft_range(const MfmaResolveArgs& a, uint32_t r, int lane)
+{
+    const uint32_t slot = a.range_slot[r];
+    const frac_grid_item rg = a.fused_fit ? a.fit.ranges[r] : frac_grid_item{};
+    if (slot >= a.nslots)
+        return;
+    resolve_dft_record(a, r, resolve_dft_eval<true>(a, slot, (int)r, lane, false), lane, rg);
+}
+
+template <bool SORTED = false, bool BY_RANGE = false>
 __global__ void __launch_bounds__(256, 8) resolve_dft(MfmaResolveArgs a)
 {
+    static_assert(SORTED || !BY_RANGE, "the range-order walk is the sorted route's");
     apply_plan(a);
     if constexpr (!SORTED) {
         if (a.paired) { // two-wave workgroups: the slot and its flipped copy at once
@@ -1854,8 +1876,13 @@ __global__ void __launch_bounds__(256, 8) resolve_dft(MfmaResolveArgs a)
     }
     // the slot is wave-uniform: readfirstlane lets its loads go through the scalar unit
     const uint32_t slot = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-    if (slot < a.nslots)
-        resolve_dft_slot<SORTED>(a, slot, threadIdx.x & 63);
+    if constexpr (BY_RANGE) {
+        if (slot < a.nr) // the wave's index is its range
+            resolve_dft_range(a, slot, threadIdx.x & 63);
+    } else {
+        if (slot < a.nslots)
+            resolve_dft_slot<SORTED>(a, slot, threadIdx.x & 63);
+    }
 }
 
 } // namespace fracenc

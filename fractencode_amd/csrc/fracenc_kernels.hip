@@ -297,16 +297,26 @@ struct FitArgs {
     frac_tuple* tuples = nullptr;
 };
 
-// tp (a tuple sink): the same record as the (domain index, transform, s, o, rms) tuple
-__device__ inline void write_fit(frac_encode_item& o, const frac_grid_item& rg, const frac_grid_item& d, int t,
-                                 double sumA, double sumA2, double sumB, double sumAB, double N, double smax,
-                                 double dist, frac_tuple* tp = nullptr, uint32_t dom = 0)
+// the fit's contrast s and brightness o from the exact sums
+struct FitCoef {
+    double s, br;
+};
+__device__ inline FitCoef fit_coef(double sumA, double sumA2, double sumB, double sumAB, double N, double smax)
 {
     const double tmp = (N * sumA2 - (sumA - 1) * sumA);
     double s = fabs(tmp) < 0.00001 ? 0.0 : (N * sumAB - sumA * sumB) / tmp;
     if (smax > 0.0)
         s = s > smax ? smax : (s < -smax ? -smax : s);
-    const double br = __fma_rn(-s, sumA, sumB) / N;
+    return FitCoef{s, __fma_rn(-s, sumA, sumB) / N};
+}
+
+// tp (a tuple sink): the same record as the (domain index, transform, s, o, rms) tuple
+__device__ inline void write_fit(frac_encode_item& o, const frac_grid_item& rg, const frac_grid_item& d, int t,
+                                 double sumA, double sumA2, double sumB, double sumAB, double N, double smax,
+                                 double dist, frac_tuple* tp = nullptr, uint32_t dom = 0)
+{
+    const FitCoef c = fit_coef(sumA, sumA2, sumB, sumAB, N, smax);
+    const double s = c.s, br = c.br;
     o.x = rg.x;
     o.y = rg.y;
     o.w = rg.w;
@@ -535,6 +545,78 @@ __device__ inline void fit_rstat_range(const FitArgs& a, uint32_t r, unsigned lo
     write_fit(a.out[r], rg, d, t, (double)sA, (double)sA2, (double)sD * 0.25, (double)X * 0.25, (double)NN, a.smax,
               dist, tp, dom);
     a.aux[r] = RangeAux{p, hit ? (uint32_t)kAuxHit : 0u};
+}
+
+// lane k's value of a wave-uniform list: one v_cndmask per further value (plain scalars — as an array the
+// compiler turns the selects into an indexed load from LDS)
+__device__ inline uint32_t lane_pick4(int lane, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3)
+{
+    uint32_t x = v0;
+    x = lane == 1 ? v1 : x;
+    x = lane == 2 ? v2 : x;
+    x = lane == 3 ? v3 : x;
+    return x;
+}
+
+// fit_rstat_range run by a whole wave (the fused n = 8 resolvers, resolve_dft): key, st and rg are wave-uniform,
+// every lane computes the same fit, and the results leave as whole stores — the 64-byte record as one 16-byte
+// store from each of lanes 0–3, the 32-byte tuple as one dword from each of lanes 0–7 (the sink is only 8-byte
+// aligned), each a single instruction over contiguous bytes. One lane storing the tuple struct split it into
+// 8 + 16 + 8 bytes, three partial writes per tuple towards a pinned sink. The default record and the fp32
+// regime's listing stay with lane 0.
+template <int N>
+__device__ inline void fit_rstat_range_wave(const FitArgs& a, uint32_t r, unsigned long long key, const uint4& st,
+                                            const frac_grid_item& rg, int lane)
+{
+    constexpr int NN = N * N;
+    frac_tuple* tp = a.tuples ? a.tuples + r : nullptr;
+    // wave-uniform by contract: through scalar registers, so the winner's loads go through the scalar unit
+    key = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(key >> 32)) << 32) |
+          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)key);
+    if (key == kKeyNone) {
+        if (lane == 0) {
+            write_default(a.out[r], rg, tp);
+            a.aux[r] = RangeAux{0u, (uint32_t)kAuxEmpty};
+        }
+        return;
+    }
+    const uint32_t p = key_pos(key);
+    const bool hit = (key >> 63) == 0;
+    const long long err = hit ? 0 : (long long)((key >> 27) & 0xffffffffull);
+    const int t = hit ? (int)(key & 7u) : (int)(a.T - 1 - (uint32_t)(key & 7u));
+    if (!hit && err >= kExactLimit) { // fp32 regime: listed; fallback_grid writes the record
+        if (lane == 0) {
+            a.aux[r] = RangeAux{p, (uint32_t)kAuxFallback};
+            a.fb_list[atomicAdd(a.fb_count, 1u)] = r;
+        }
+        return;
+    }
+    const uint32_t dom = a.porig[p];
+    const frac_grid_item d = a.doms[dom];
+    const long long X = (uint32_t)__builtin_amdgcn_readfirstlane((int)st.x);
+    const uint32_t sy = (uint32_t)__builtin_amdgcn_readfirstlane((int)st.y);
+    const long long sD = sy & 0xffffu, sA = sy >> 16;
+    const long long sD2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)st.z);
+    const long long sA2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)st.w);
+    const long long S16 = 16 * sA2 - 8 * X + sD2;
+    const double dist = ((double)S16 * 0.0625) / (double)(d.w * d.h);
+    const FitCoef c = fit_coef((double)sA, (double)sA2, (double)sD * 0.25, (double)X * 0.25, (double)NN, a.smax);
+    const uint32_t s0 = (uint32_t)__double2loint(c.s), s1 = (uint32_t)__double2hiint(c.s);
+    const uint32_t b0 = (uint32_t)__double2loint(c.br), b1 = (uint32_t)__double2hiint(c.br);
+    const uint32_t e0 = (uint32_t)__double2loint(dist), e1 = (uint32_t)__double2hiint(dist);
+    // frac_encode_item as four uint4: the range, {distance, contrast}, {brightness, transform, _pad}, the domain
+    const uint4 q = make_uint4(lane_pick4(lane, rg.x, e0, b0, d.x), lane_pick4(lane, rg.y, e1, b1, d.y),
+                               lane_pick4(lane, rg.w, s0, (uint32_t)t, d.w), lane_pick4(lane, rg.h, s1, 0u, d.h));
+    if (lane < 4)
+        reinterpret_cast<uint4*>(&a.out[r])[lane] = q; // 64-byte records in device memory: 16-byte aligned
+    if (tp) {
+        // frac_tuple's eight dwords: {domain, transform, s, o, distance}
+        const uint32_t lo = lane_pick4(lane, dom, (uint32_t)t, s0, s1), hi = lane_pick4(lane - 4, b0, b1, e0, e1);
+        if (lane < 8)
+            reinterpret_cast<uint32_t*>(tp)[lane] = lane < 4 ? lo : hi;
+    }
+    if (lane == 0)
+        a.aux[r] = RangeAux{p, hit ? (uint32_t)kAuxHit : 0u};
 }
 
 template <int N>

@@ -928,7 +928,11 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
     v.flip_slots = 0;
     if (c->dft_copies != 1 || c->p.transforms != 4)
         return c->fail(FRAC_E_STATE, "SEA tiled form: T = 4 only (resolve_dft<true> has no flipped copies)");
-    resolve_dft<true><<<std::max(1u, (v.nslots + 3) / 4), 256, 0, c->stream>>>(v);
+    // tuples bound for host memory leave in range order (one wave per range), else one wave per slot
+    if (kTpRangeOrder && v.fit.tuples && c->tuple_sink_host)
+        resolve_dft<true, true><<<std::max(1u, (nr + 3) / 4), 256, 0, c->stream>>>(v);
+    else
+        resolve_dft<true><<<std::max(1u, (v.nslots + 3) / 4), 256, 0, c->stream>>>(v);
     return FRAC_OK;
 }
 
