@@ -201,23 +201,42 @@ def ref_estimate(plane: np.ndarray, src_size: int, tgt_size: int, T: int = 4, th
 
 
 def quadtree(plane: np.ndarray, max_size: int, min_size: int, split_distance: float, T: int = 4,
-             use_classifier: bool = False, thr: float = 0.0, smax: float = -1.0):
+             use_classifier: bool = False, thr: float = 0.0, smax: float = -1.0, tgt: np.ndarray | None = None,
+             stats: bool = False):
     """The quadtree rule of include/fracenc.h (frac_encode_quadtree) restated on the oracle: per
     level n, ranges searched against createUniformGrid(W, H, 2n, n); a range whose distance
     exceeds split_distance (n > min_size) is replaced by its four quadrants.  No reference
-    exists (main.cpp:75-76 ignores --quadtree); each level's search is the pinned oracle."""
+    exists (main.cpp:75-76 ignores --quadtree); each level's search is the pinned oracle.
+    tgt: the target plane (of plane's size) the ranges are read and classified on, the domains on
+    `plane`, as estimate(..., tgt=).  stats=True also returns a dict summed over the levels:
+    rejected (as estimate returns it), empty (records with dw == 0 over every searched range, those
+    that then split included), searched / split (ranges searched / split per level, keyed by size).
+    A grid whose item does not fit the frame is empty, as frac_uniform_grid's is: the reference's loop
+    (uniform_grid) emits one item at (0, 0) even then, which lies outside the plane."""
     plane = np.ascontiguousarray(plane, dtype=np.uint8)
+    tplane = plane if tgt is None else np.ascontiguousarray(tgt, dtype=np.uint8)
+    if tplane.shape != plane.shape:
+        raise ValueError("quadtree: source and target planes must have one size")
     H, W = plane.shape
-    pending = uniform_grid(W, H, max_size, max_size)
+
+    def grid(size, offset):
+        return uniform_grid(W, H, size, offset) if W >= size and H >= size else np.zeros(0, dtype=ITEM_DTYPE)
+
+    pending = grid(max_size, max_size)
     out = []
+    tot = {"rejected": 0, "empty": 0, "searched": {}, "split": {}}
     n = max_size
     while len(pending) and n >= min_size:
-        doms = uniform_grid(W, H, 2 * n, n)
+        doms = grid(2 * n, n)
         rngs = pending
         if use_classifier:
             doms = classify(plane, doms)
-            rngs = classify(plane, rngs)
-        res, _, _ = estimate(plane, doms, rngs, T=T, thr=thr, smax=smax, use_classifier=use_classifier)
+            rngs = classify(tplane, rngs)
+        res, rej, _ = estimate(plane, doms, rngs, T=T, thr=thr, smax=smax, use_classifier=use_classifier,
+                               tgt=None if tgt is None else tplane)
+        tot["rejected"] += rej
+        tot["empty"] += int((res["dw"] == 0).sum())
+        tot["searched"][n] = len(res)
         nxt = []
         for i, r in enumerate(res):
             if n > min_size and r["dist"] > split_distance:
@@ -226,6 +245,7 @@ def quadtree(plane: np.ndarray, max_size: int, min_size: int, split_distance: fl
                 nxt += [(x, y, h, h, -1), (x + h, y, h, h, -1), (x, y + h, h, h, -1), (x + h, y + h, h, h, -1)]
             else:
                 out.append((r, n))
+        tot["split"][n] = len(nxt) // 4
         pending = np.array(nxt, dtype=ITEM_DTYPE)
         n //= 2
     recs = np.zeros(len(out), dtype=RESULT_DTYPE)
@@ -233,4 +253,4 @@ def quadtree(plane: np.ndarray, max_size: int, min_size: int, split_distance: fl
     for i, (r, sz) in enumerate(out):
         recs[i] = r
         sizes[i] = sz
-    return recs, sizes
+    return (recs, sizes, tot) if stats else (recs, sizes)

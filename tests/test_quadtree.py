@@ -9,6 +9,7 @@ import pytest
 
 import fractencode_amd as F
 from golden_util import plane
+from quadtree_frames import as_oracle as _as_oracle, leaves_from_records as _leaves_from_records
 
 
 def _coverage(recs, sizes, W, H, max_size):
@@ -29,16 +30,6 @@ def test_oracle_quadtree_partition_properties(oracle, split):
     if split == 0.0:  # only exact matches stop the split
         assert (recs["dist"][sizes > 4] == 0.0).all()
     assert set(np.unique(sizes)) <= {4, 8, 16}
-
-
-def _as_oracle(items):
-    from oracle.oracle import RESULT_DTYPE
-
-    out = np.zeros(len(items), dtype=RESULT_DTYPE)
-    for a, b in (("x", "x"), ("y", "y"), ("dx", "dx"), ("dy", "dy"), ("sw", "dw"), ("sh", "dh"), ("transform", "t"),
-                 ("distance", "dist"), ("contrast", "s"), ("brightness", "o")):
-        out[b] = items[a]
-    return out
 
 
 @pytest.mark.gpu
@@ -231,21 +222,6 @@ def test_gpu_quadtree_levels_into_pinned_memory_across_frames(leaves):
             part, sp = e.encode_quadtree(16, 4, 0.05, out=pinned[:m], leaves=leaves, allow_short=True)
             assert sp["items"] == len(want) and part.tobytes() == want[:m].tobytes(), k
             assert not pinned[m:].tobytes().strip(b"\0"), k  # nothing past the capacity
-
-
-def _leaves_from_records(rec, W):
-    """numpy restatement of frac_qt_leaf packing (include/fracenc.h): the test's independent packer."""
-    n = rec["w"].astype(np.int64)
-    cols = (W - 2 * n) // n + 1
-    has = rec["sw"] != 0
-    d = np.where(has, (rec["dy"].astype(np.int64) // n) * cols + rec["dx"].astype(np.int64) // n, F.QT_NO_DOMAIN)
-    lv = np.log2(n).astype(np.int64)
-    out = np.zeros(len(rec), dtype=F.QT_LEAF)
-    out["x"], out["y"] = rec["x"], rec["y"]
-    out["code"] = (d & 0xFFFFFF) | ((rec["transform"].astype(np.int64) & 15) << 24) | (lv << 28)
-    for k in ("contrast", "brightness", "distance"):
-        out[k] = rec[k]
-    return out
 
 
 def test_records_from_leaves_round_trip():
