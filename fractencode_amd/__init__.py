@@ -341,6 +341,8 @@ class Engine:
 
     def set_params(self, transforms=None, use_classifier=None, rms_threshold=None, s_max=None, engine=None,
                    flags=None):
+        """Change the given parameters of a prepared context (frac_set_params); the next run() re-prepares.  Like
+        every setter it ends the last run's results: until the next run() the readers raise FracError."""
         if transforms is not None:
             self._p.transforms = transforms
         if use_classifier is not None:
@@ -598,6 +600,8 @@ class Engine:
         return y, u, v
 
     def device_results_ptr(self) -> int:
+        """The device address of the last run's records; 0 when none are readable (no run yet, or a setter
+        called since the last one)."""
         return lib().frac_device_results(self._ctx) or 0
 
 

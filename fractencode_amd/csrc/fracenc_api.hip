@@ -207,6 +207,17 @@ frac_ctx* frac_create(int device, const frac_params* params)
 
 void frac_destroy(frac_ctx* c) { delete c; } // ~frac_ctx: idle first, then every member frees itself
 
+// A change of parameters, domains or ranges ends the last run's results: until the next frac_run every reader
+// refuses them (FRAC_E_STATE) rather than pair the old winners with the new parameters or lists.  The run's
+// unsettled fp32 fallback goes with them: nothing may read its records any more, and its saved arguments
+// name buffers the next prepare() may reallocate.  (The plane setters clear `ran` in planes_changed; they settle
+// the fallback instead, before their upload overwrites the plane it reads.)
+static void results_gone(frac_ctx* c)
+{
+    c->ran = false;
+    c->fb_pending = false;
+}
+
 int frac_set_params(frac_ctx* c, const frac_params* params)
 {
     if (!c)
@@ -216,6 +227,7 @@ int frac_set_params(frac_ctx* c, const frac_params* params)
         return c->fail(FRAC_E_INVALID, msg);
     c->p = *params;
     c->dirty = true;
+    results_gone(c);
     return FRAC_OK;
 }
 
@@ -347,6 +359,7 @@ int frac_set_domains(frac_ctx* c, const frac_grid_item* d, size_t nd)
     c->doms_uploaded = false;
     c->doms_trusted = false;
     c->dirty = true;
+    results_gone(c);
     return FRAC_OK;
 }
 
@@ -360,7 +373,7 @@ int frac_set_ranges(frac_ctx* c, const frac_grid_item* r, size_t nr)
     c->ranges_set = true;
     c->ranges_dev = false;
     c->dirty = true;
-    c->ran = false;
+    results_gone(c);
     return FRAC_OK;
 }
 
@@ -570,6 +583,10 @@ const frac_encode_item* frac_device_results(frac_ctx* c)
 {
     if (!c)
         return nullptr;
+    if (!c->ran) { // no run yet, or a setter since the last one: d_out holds nothing of the current state
+        c->fail(FRAC_E_STATE, "no results: frac_run has not been called");
+        return nullptr;
+    }
     // work enqueued on the context's stream after this call reads complete records
     if (c->fb_pending && (hipSetDevice(c->device) != hipSuccess || settle_fallback(c) != FRAC_OK))
         return nullptr;

@@ -152,12 +152,23 @@ int frac_device_count(void);
 frac_ctx* frac_create(int device, const frac_params* params);
 void frac_destroy(frac_ctx* ctx);
 const char* frac_last_error(const frac_ctx* ctx);
+/* When results are readable.  A context is meant to live long: frame after frame, with parameters, grids and
+ * planes changed between runs.  The results of a run are readable from that frac_run until the next call of
+ * a setter — frac_set_params, frac_set_domains, frac_set_ranges, frac_set_frame, frac_set_planes,
+ * frac_set_frame_device, frac_set_frame_device_async, frac_set_frame_async — or of frac_encode_quadtree /
+ * frac_encode_quadtree_leaves (which search lists of their own).  From such a call to the next frac_run every
+ * reader — frac_fetch, frac_fetch_tuples, frac_copy_tuples_device, frac_copy_results_device, frac_pack_frc1,
+ * frac_decode_results — returns FRAC_E_STATE, and frac_device_results returns NULL: the old winners are never
+ * paired with the new parameters, domain list, ranges or planes.  A setter that fails its own argument checks
+ * changes nothing.  frac_set_stream, frac_set_tuple_sink, frac_sync, frac_classify_items, frac_decode,
+ * frac_decode_frc1 and the colour conversion leave the results readable. */
 int frac_set_params(frac_ctx* ctx, const frac_params* params);
 
 /* Planes are uint8, row-major with the given stride (bytes). Copied to the device.
  * frac_set_frame: source == target (what Encoder2 does, encode/Encoder2.hpp:36).
  * frac_set_planes: distinct source (domain) and target (range) planes, as
- * TransformEstimator2's constructor allows (encode/TransformEstimator2.hpp:15-21). */
+ * TransformEstimator2's constructor allows (encode/TransformEstimator2.hpp:15-21).
+ * Every plane setter below ends the last run's results until the next frac_run. */
 int frac_set_frame(frac_ctx* ctx, const uint8_t* plane, uint32_t w, uint32_t h, uint32_t stride);
 int frac_set_planes(frac_ctx* ctx, const uint8_t* src, uint32_t sw, uint32_t sh, uint32_t sstride,
                     const uint8_t* tgt, uint32_t tw, uint32_t th, uint32_t tstride);
@@ -177,7 +188,8 @@ int frac_set_frame_device_async(frac_ctx* ctx, const void* d_plane, uint32_t w, 
  * after this call. */
 int frac_set_frame_async(frac_ctx* ctx, const uint8_t* plane, uint32_t w, uint32_t h, uint32_t stride);
 
-/* The domain pool (TransformEstimator2's sourceGrid) and the range list. */
+/* The domain pool (TransformEstimator2's sourceGrid) and the range list.  Either call, like
+ * frac_set_params and the plane setters, ends the last run's results until the next frac_run. */
 int frac_set_domains(frac_ctx* ctx, const frac_grid_item* domains, size_t nd);
 int frac_set_ranges(frac_ctx* ctx, const frac_grid_item* ranges, size_t nr);
 
@@ -208,8 +220,9 @@ int frac_search(frac_ctx* ctx, const frac_grid_item* ranges, size_t nr, frac_enc
  * enqueued on its previous stream comes before anything it enqueues on the new one (an event). */
 int frac_set_stream(frac_ctx* ctx, void* hip_stream);
 void* frac_get_stream(frac_ctx* ctx);
-/* Device pointer to the nr frac_encode_item results of the last run (valid until
- * the next set_ranges / destroy); used for device-side gathers (RCCL). */
+/* Device pointer to the nr frac_encode_item results of the last run (valid until the next setter call,
+ * frac_run or destroy; see "When results are readable"); used for device-side gathers (RCCL).  NULL when
+ * no results are readable: before the first frac_run, and between a setter call and the next frac_run. */
 const frac_encode_item* frac_device_results(frac_ctx* ctx);
 /* Asynchronous device-to-device copy of the last run's nr results into d_dst
  * (ordered on the context's stream). */
