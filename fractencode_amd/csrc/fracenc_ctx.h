@@ -231,11 +231,11 @@ struct frac_ctx {
     TpBuckets tp_bk{};
     std::vector<uint4> tp_groups;
     uint32_t tp_key_bits = 16; // (bucket << 16 | Σ) sort keys: 16 + ⌈log2 nb⌉ bits
-    std::vector<uint32_t> tp_iota;
     std::vector<uint2> tp_blk_group;
     DBuf<uint4> d_tp_groups;
     DBuf<uint2> d_tp_blk_group, d_tp_tile_sd, d_tp_blk_sr;
-    DBuf<uint32_t> d_tp_blk_u, d_tp_nch, d_tp_choff, d_tp_iota, d_tp_pairs, d_tp_row_of;
+    DBuf<uint32_t> d_tp_blk_u, d_tp_pairs, d_tp_row_of;
+    DBuf<uint4> d_tp_rec;     // [nblocks·64] search_dft CHUNKED's record per block and lane (DftArgs::rec)
     struct TpTotals {
         uint32_t w[8];
     };
@@ -243,7 +243,7 @@ struct frac_ctx {
     // the tiled form's own maps and work lists, in its sorted layout (rebuilt every run): under AUTO the
     // MFMA engine's domain-ordered ones (d_m_tile_pos, the slot maps, d_m8_*) stay prepared beside them
     DBuf<int32_t> d_tp_slot_range, d_tp_tile_pos;
-    DBuf<uint32_t> d_tp_range_slot, d_tp_blk_ptr, d_tp_blk_ent;
+    DBuf<uint32_t> d_tp_range_slot;
     DBuf<uint4> d_tp_work;
     DBuf<unsigned long long> d_tp_sevals; // per group, the (range, domain) pairs of its seed tile
     // FRAC_ENGINE_AUTO's pruned route (select_engine): the tiled form's windows first, the exhaustive

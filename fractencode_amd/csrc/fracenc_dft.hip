@@ -47,6 +47,9 @@
 //             (App. A.3), as with the direct engine.
 // The per-lane chunk maximum of y and the tile it appeared in feed resolve_dft, which
 // re-derives the exact (domain, transform) inside the chunk with integer arithmetic.
+// resolve_dft reads, per slot: the exhaustive route's per-work-item entries through the block → entry CSR map
+// (SORTED = false), or the search's own merge (slotbest), or, on the SEA tiled form (SORTED = true), the two
+// records search_dft<…, CHUNKED> left for the slot's row halves — no map and no walk over chunks.
 #include "fracenc_common.h"
 
 namespace fracenc {
@@ -187,7 +190,9 @@ struct DftArgs {
                           //            form: R6 = Σ_o(|s_a + u_a| + |s_a − u_a|))
     uint2* tguard;        // [ntiles]   {max 4·D∞, max Σb²} over the tile's valid rows (five- / six-MFMA
                           //            layout: {max 2·D6, max Σb²})
-    const uint32_t* choff; // CHUNKED: [work] first chunk entry of the work item (fracenc_tp.hip)
+    uint4* rec = nullptr;  // CHUNKED: [nblocks·64] per block and lane the window's maximum and the chunks attaining
+                           // it, {bits of max y (+inf = hit), n chunks attaining it, the first's word, the second's}
+                           // with a chunk's word tile | tile mask << 28 (fracenc_tp.hip)
     const int32_t* trmax;  // kDftFast6: [ntiles] the largest block R6 whose guard holds against the
                            // tile, (kFast6Limit − max Σb²) / max 2·D6 (−1: none)
     unsigned long long* stamps = nullptr; // FRAC_CLOCK_STAMP builds only: [workgroups][kClockStampWords]
@@ -1239,10 +1244,16 @@ __device__ inline void stage_tiles_buf(uint4* dst, __amdgpu_buffer_rsrc_t ra, __
 }
 
 constexpr uint32_t kDftBlocksPerWG = 8; // waves (range blocks) sharing one LDS domain stage
+// chunks a CHUNKED record lists by word (K of DESIGN §7.7); its count of attaining chunks is exact, so
+// the resolve tells "all listed" from "more than listed"
+constexpr uint32_t kTpRecList = 2;
 
 // CHUNKED (the SEA engine's tiled form, fracenc_tp.hip): tiles are in ΣD4 order, not domain
-// order, so instead of the first chunk attaining each lane's maximum every chunk's maximum is
-// written, entry ((choff[work] + chunk)·WAVES + wave)·64 + lane, and resolve_dft keeps all ties.
+// order, so every chunk attaining a lane's maximum matters, not only the first.  One workgroup holds a
+// group's whole window and wave w its block wk.x + w throughout, so the lane keeps the running maximum,
+// the number of chunks attaining it and the words of the first kTpRecList of them in registers, and
+// writes one record per lane when the window is done (DftArgs::rec): no per-chunk entries.  resolve_dft
+// re-evaluates the listed chunks, or the whole window when more than the list holds attain the maximum.
 // TMASK (not CHUNKED, slotbest): each lane also tracks which tiles of its best chunk attain its maximum (or
 // hold a hit), and the slot word carries them, so resolve_dft re-evaluates those tiles instead of the whole
 // chunk.  Costs the tile-pair epilogue a compare per tile: chosen where the resolve, not the search, dominates.
@@ -1291,10 +1302,12 @@ __global__ void __launch_bounds__(64 * WAVES) search_dft(DftArgs d)
     float best = -__builtin_inff();
     uint32_t btile = 0, bmask = 0xfu;
     uint32_t masks[2] = {0u, 0u};
+    uint32_t nbest = 0, word1 = 0, word2 = 0; // CHUNKED: chunks attaining `best`, the first two's words
     auto finish_stage = [&](float cm, uint32_t tb) {
         if constexpr (CHUNKED) {
-            static_assert(TPS == 4, "chunk entries assume 4-tile stages");
-            // the entry carries the chunk's tile mask in bits 28..31 of its tile (resolve_dft<true>
+            static_assert(TPS == 4, "chunk words assume 4-tile stages");
+            static_assert(kTpRecList == 2, "the record lists two chunks");
+            // the chunk's word carries its tile mask in bits 28..31 of its tile (resolve_dft<true>
             // evaluates only those tiles): the hit tiles when the chunk holds a hit, else the
             // tiles attaining the maximum
             uint32_t msk = masks[0];
@@ -1303,9 +1316,13 @@ __global__ void __launch_bounds__(64 * WAVES) search_dft(DftArgs d)
                     cm = __builtin_inff();
                     msk = masks[1];
                 }
-            if (active)
-                a.entries[((size_t)(d.choff[blockIdx.x] + (tb - wk.z) / 4u) * WAVES + wv) * 64 + lane] =
-                    make_uint2(__float_as_uint(cm * kOut), tb | (msk << 28));
+            const uint32_t word = tb | (msk << 28);
+            // (a chunk's maximum is finite or +inf, so the first chunk always starts the list)
+            const bool gt = cm > best, eq = cm == best;
+            word2 = (eq && nbest == 1u) ? word : word2;
+            word1 = gt ? word : word1;
+            nbest = gt ? 1u : nbest + (eq ? 1u : 0u);
+            best = gt ? cm : best;
             masks[0] = masks[1] = 0u;
             return;
         }
@@ -1388,6 +1405,11 @@ __global__ void __launch_bounds__(64 * WAVES) search_dft(DftArgs d)
         }
     }
 #endif
+    if constexpr (CHUNKED) {
+        // an empty window leaves {−inf, 0}: resolve_dft gives the slot the default record
+        if (active)
+            d.rec[(size_t)blk * 64 + lane] = make_uint4(__float_as_uint(best * kOut), nbest, word1, word2);
+    }
     if (active && !CHUNKED) {
         if (d.slotbest) {
             // lanes l and l + 32 hold one range slot's two row halves: the greater y, among equal y the earlier
@@ -1547,9 +1569,17 @@ __device__ inline DftResolved resolve_dft_eval(const MfmaResolveArgs& a, uint32_
     const int i = lane >> 2, g = lane & 3;
     const uint4* rp4 = reinterpret_cast<const uint4*>(a.rorb + (size_t)slot * 32 + g * (PG / 2));
     const uint4 r0 = rp4[0], r1 = rp4[1];
+    const uint32_t blk = slot >> 5, col = slot & 31u;
+    // SORTED: the slot's two records (its row halves: lanes col and col + 32 of its block) and the block's group
+    uint4 rec0 = make_uint4(0u, 0u, 0u, 0u), rec1 = rec0;
+    uint2 gw = make_uint2(0xffffffffu, 0u);
+    if constexpr (SORTED) {
+        rec0 = a.rec[(size_t)blk * 64 + col];
+        rec1 = a.rec[(size_t)blk * 64 + col + 32];
+        gw = a.blk_group[blk];
+    }
     if (ri < 0)
         return res;
-    const uint32_t blk = slot >> 5, col = slot & 31u;
     // lane (i, g) holds orbits 4g..4g+3 of the range as pixel pairs (dft_range_prep) and meets
     // the same orbits of a domain row (tile-order pool, dft_domain_build). With fwd(t) = g^t,
     //   X_t = Σ_q r(q)·D4(fwd_t q) = Σ_{o,k} r_{o,k}·D_{o,k+t}:
@@ -1582,9 +1612,9 @@ __device__ inline DftResolved resolve_dft_eval(const MfmaResolveArgs& a, uint32_
         target = exact && !sentinel ? sa16 - (int64_t)vmax : -1;
         hit = a.hitH >= 0 && (sentinel || (target >= 0 && target <= a.hitH));
     };
-    // re-evaluate chunk `tile0` (4 tiles from there; SORTED: the tiles in tmask) on the rows of lane half h,
-    // keeping the least selection key
-    auto eval_chunk = [&](uint32_t tile0, uint32_t h, uint32_t tmask) {
+    // re-evaluate chunk `tile0` (4 tiles from there, none at or past tend; SORTED: the tiles in tmask) on the rows
+    // of lane half h, keeping the least selection key
+    auto eval_chunk = [&](uint32_t tile0, uint32_t h, uint32_t tmask, uint32_t tend) {
         const int row = (i & 3) + 8 * (i >> 2) + 4 * (int)h;
         if (!exact) {
             // fp32 fallback regime: every candidate has S16 ≥ 2^24; any valid domain of the
@@ -1597,7 +1627,7 @@ __device__ inline DftResolved resolve_dft_eval(const MfmaResolveArgs& a, uint32_
             }
             return;
         }
-        for (uint32_t tile = tile0; tile < min(tile0 + (uint32_t)kTilesPerStage, a.ntiles); ++tile) {
+        for (uint32_t tile = tile0; tile < min(tile0 + (uint32_t)kTilesPerStage, tend); ++tile) {
             if (!((tmask >> (tile - tile0)) & 1u))
                 continue;
             // the row's pool position (for the key) and its D4 from the tile-order copy are
@@ -1697,7 +1727,37 @@ __device__ inline DftResolved resolve_dft_eval(const MfmaResolveArgs& a, uint32_
         const uint32_t hm = (uint32_t)sb & 3u;
         for (uint32_t h = 0; h < 2; ++h)
             if ((hm >> h) & 1u)
-                eval_chunk(tile0, h, tm);
+                eval_chunk(tile0, h, tm, a.ntiles);
+    } else if constexpr (SORTED) {
+        // the search kept each lane's maximum over its group's window and the chunks attaining it (search_dft
+        // CHUNKED): two loads per slot, no CSR walk.  A block without a group (a bucket without domains) was
+        // never searched and its record is some earlier run's: not read
+        if (gw.x == 0xffffffffu)
+            return res;
+        const float y0 = __uint_as_float(rec0.x), y1 = __uint_as_float(rec1.x);
+        vmax = __builtin_fmaxf(y0, y1);
+        if (!(vmax > -1.0e29f))
+            return res; // an empty window, or only padding rows: no eligible domain, best_key stays "none"
+        set_target();
+        for (uint32_t h = 0; h < 2; ++h) {
+            const uint4 rc = h ? rec1 : rec0;
+            if (__uint_as_float(rc.x) != vmax)
+                continue;
+            if (rc.y <= kTpRecList) {
+                // every chunk attaining the maximum is listed; a word carries the chunk's tile mask in bits 28..31
+                eval_chunk(rc.z & 0x0fffffffu, h, rc.z >> 28, a.ntiles);
+                if (rc.y > 1u)
+                    eval_chunk(rc.w & 0x0fffffffu, h, rc.w >> 28, a.ntiles);
+            } else {
+                // more chunks attain it than the record lists: every chunk of the group's window, whole.  A chunk
+                // that does not hold the maximum adds nothing (only rows with S16 = target, or hits, are kept), so
+                // this is exact; the window ends at its t1, not the chunk's fourth tile: past it lie tiles the
+                // bound excluded, or another bucket's
+                const uint4 wk = a.work[gw.x];
+                for (uint32_t t = wk.z; t < wk.w; t += (uint32_t)kTilesPerStage)
+                    eval_chunk(t, h, 0xfu, wk.w);
+            }
+        }
     } else {
         const uint32_t e0 = a.blk_ptr[blk], e1 = a.blk_ptr[blk + 1];
         const uint32_t nent = (e1 - e0) * 2u;
@@ -1730,12 +1790,8 @@ __device__ inline DftResolved resolve_dft_eval(const MfmaResolveArgs& a, uint32_
                 const int src = __ffsll((long long)match) - 1;
                 match &= match - 1;
                 const uint32_t j = c0 + (uint32_t)src;
-                uint32_t ey = (uint32_t)__builtin_amdgcn_readlane((int)enl.y, src);
-                // SORTED entries carry the chunk's tile mask in bits 28..31 (search_dft CHUNKED)
-                const uint32_t tmask = SORTED ? (ey >> 28) : 0xfu;
-                if constexpr (SORTED)
-                    ey &= 0x0fffffffu;
-                eval_chunk(ey, j & 1u, tmask);
+                const uint32_t ey = (uint32_t)__builtin_amdgcn_readlane((int)enl.y, src);
+                eval_chunk(ey, j & 1u, 0xfu, a.ntiles);
             }
         }
     }
@@ -1838,16 +1894,17 @@ __device__ inline void resolve_dft_pair(const MfmaResolveArgs& a, uint32_t slot,
     }
 }
 
-// One wave per slot, in slot order (the 32 ranges of a block read the same entry lines back to
-// back); launched as one- or four-wave workgroups. A grid of fewer, longer-lived waves striding over the slots measured slower (452 vs
+// One wave per slot, in slot order (the 32 ranges of a block read the same entry lines, or on the sorted route
+// neighbouring records, back to back); launched as one- or four-wave workgroups. A grid of fewer, longer-lived waves striding over the slots measured slower (452 vs
 // 372 µs at C3 in the SEA tiled form).
 //
 // BY_RANGE (the sorted route writing a tuple sink in host memory, launch_tp): one wave per range in range order
 // instead (slot = range_slot[r], padding slots never visited, grid ⌈nr / 4⌉), so neighbouring waves write
 // neighbouring tuples — the four waves of a workgroup 128 contiguous bytes of the sink — as the exhaustive route's
 // slot walk does.  In (bucket, ΣR) order no two tuples written near each other in time share a host line, which cost
-// the C3 finish 0.12 ms across PCIe; the price of range order is that a block's 32 slots no longer read its entry
-// rows back to back, 0.05 ms at C3, so a run without a host sink keeps the slot order.
+// the C3 finish 0.12 ms across PCIe.  Range order still has a price without the entry rows it once
+// scattered: a block's 32 slots no longer read their records, constants and orbit copies side by side, 0.035 ms of
+// the C3 finish with no sink or a device sink (§7.7), so a run without a host sink keeps the slot order.
 // kTpRangeOrder = false keeps the slot order everywhere.
 constexpr bool kTpRangeOrder = true;
 

@@ -685,12 +685,13 @@ int launch_mfma(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool inits =
 }
 
 // SEA engine, tiled form (fracenc_tp.hip): sorted tiles and blocks, per-range seed bounds,
-// per-group windows, the Fourier search over the windows with per-chunk entries, resolve_dft.
-// One host synchronisation sizes the entry arrays (their count depends on the windows).
-// Outside the two sorts the route is ten commands: tp_keys (with the run's resets), tp_build, tp_prep, the seed
-// search_dft, tp_seed_windows, tp_plan, the synchronisation, tp_fill_entries, search_dft and resolve_dft.
+// per-group windows, the Fourier search over the windows with one record per block and lane, resolve_dft.
+// No buffer is sized from the windows (the records are nblocks·64, allocated at prepare()); one host
+// synchronisation remains, for the run's totals: frac_stats' counts and the budget test.
+// Outside the two sorts the route is nine commands: tp_keys (with the run's resets), tp_build, tp_prep, the seed
+// search_dft, tp_seed_windows, tp_plan (the totals), the synchronisation, search_dft and resolve_dft.
 // budgeted (FRAC_ENGINE_AUTO's pruned route): when the windows hold more than kAutoPruneBudget of the run's
-// block × tile pairs the attempt is abandoned before any entry array is sized from them, and the exhaustive
+// block × tile pairs the attempt is abandoned before the windowed search is launched, and the exhaustive
 // Fourier search (launch_dft) produces the records in the same run on the same stream.
 int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, bool budgeted = false)
 {
@@ -846,10 +847,8 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
     da.rguard = c->d_dft_rguard.ptr;
     da.tguard = c->d_dft_tguard.ptr;
     da.trmax = nullptr; // kTpVar runs the exact epilogue only
-    // seed: the Fourier search over one tile per group, one chunk entry per wave (choff = group)
-    FRAC_HIP(c, c->d_m_entries.ensure((size_t)ng * W8 * 64));
-    da.m.entries = c->d_m_entries.ptr;
-    da.choff = c->d_tp_iota.ptr;
+    // seed: the Fourier search over one tile per group, into the records the windowed search writes again
+    da.rec = c->d_tp_rec.ptr;
     search_dft<false, kTpVar, W8, 4, true><<<ng, 64 * W8, 0, c->stream>>>(da);
     // per group: its blocks' seed bounds, then its window
     TpWindowArgs w;
@@ -857,25 +856,22 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
     w.ngroups = ng;
     w.blk_sr = c->d_tp_blk_sr.ptr;
     w.blk_u = c->d_tp_blk_u.ptr;
-    w.entries = c->d_m_entries.ptr;
+    w.rec = c->d_tp_rec.ptr;
     w.slot_range = c->d_tp_slot_range.ptr;
     w.rconst = c->d_m_rconst.ptr;
     w.tile_sd = c->d_tp_tile_sd.ptr;
     w.hitH = c->hitH;
     w.work = c->d_tp_work.ptr;
-    w.nchunks = c->d_tp_nch.ptr;
     w.pairs = c->d_tp_pairs.ptr;
     w.bk = c->tp_bk;
     w.evals = c->d_tp_evals.ptr;
     w.sevals = c->d_tp_sevals.ptr;
     tp_seed_windows<<<ng, 256, 0, c->stream>>>(w);
-    // the chunk and entry offsets, and the totals (sizes of the entry arrays, the searched pairs) written
-    // straight into the host's pinned block
+    // the totals (the searched pairs and evaluations) written straight into the host's pinned block
     void* dtot = nullptr;
     FRAC_HIP(c, hipHostGetDevicePointer(&dtot, c->h_tp_tot.ptr, 0));
-    tp_plan<<<1, kTpPlanThreads, 0, c->stream>>>(c->d_tp_nch.ptr, ng, c->d_tp_blk_group.ptr, nbk, c->d_tp_pairs.ptr,
-                                                 c->d_tp_evals.ptr, c->d_tp_sevals.ptr, c->d_tp_choff.ptr,
-                                                 c->d_tp_blk_ptr.ptr, reinterpret_cast<uint32_t*>(dtot));
+    tp_plan<<<1, kTpPlanThreads, 0, c->stream>>>(ng, c->d_tp_pairs.ptr, c->d_tp_evals.ptr, c->d_tp_sevals.ptr,
+                                                 reinterpret_cast<uint32_t*>(dtot));
     FRAC_HIP(c, hipStreamSynchronize(c->stream));
     uint32_t tot[8];
     for (int k = 0; k < 8; ++k)
@@ -888,7 +884,7 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
         if (pairs * kAutoPruneBudgetDen > c->tp_full_pairs * kAutoPruneBudgetNum) {
             if (getenv("FRAC_TRACE"))
                 fprintf(stderr, "[frac auto] windows %llu of %llu block x tile pairs: over the budget, exhaustive search "
-                                "(no entry array sized)\n", (unsigned long long)pairs, (unsigned long long)c->tp_full_pairs);
+                                "(windowed search not launched)\n", (unsigned long long)pairs, (unsigned long long)c->tp_full_pairs);
             // launch_dft reads the MFMA route's own maps and lists and rebuilds every frame-derived buffer in
             // dft_prep (fill_tp); best_key and fb_count were reset by tp_keys and nothing has written them
             FRAC_TRY(launch_dft(c, dtgt, tstride, false, false));
@@ -899,20 +895,18 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
         c->flops_ran = seed_flops;
         c->evaluated_ran = seed_evals;
     }
-    FRAC_HIP(c, c->d_m_entries.ensure((size_t)tot[0] * kDftBlocksPerWG * 64));
-    FRAC_HIP(c, c->d_tp_blk_ent.ensure(tot[1]));
-    tp_fill_entries<<<(nbk + 255) / 256, 256, 0, c->stream>>>(c->d_tp_blk_group.ptr, c->d_tp_choff.ptr,
-                                                              c->d_tp_blk_ptr.ptr, nbk, c->d_tp_blk_ent.ptr);
     // issued matrix work (8 MFMA 32×32×16 per block × tile) and the (range, domain) pairs in the windows
     // (padding slots and rows of partial blocks and tiles are no pairs)
     c->flops_ran += pairs * (kDftTpForm == 6 ? 6ull : 8ull) * 32768ull;
     c->evaluated_ran += (uint64_t)tot[4] | ((uint64_t)tot[5] << 32);
-    da.m.entries = c->d_m_entries.ptr;
-    da.choff = c->d_tp_choff.ptr;
     launch_search_dft<kTpVar, W8, 4, true>(c, da, ng, c->hitH > 0);
     if (timing)
         FRAC_TRY(mark_event(c, 2));
-    MfmaResolveArgs v = resolve_args(c, dtgt, tstride, nr, c->d_tp_blk_ptr.ptr, c->d_tp_blk_ent.ptr);
+    MfmaResolveArgs v = resolve_args(c, dtgt, tstride, nr, nullptr, nullptr); // (records, no CSR map)
+    v.entries = nullptr;
+    v.rec = c->d_tp_rec.ptr;
+    v.blk_group = c->d_tp_blk_group.ptr;
+    v.work = c->d_tp_work.ptr;
     v.T = 4;
     v.slot_range = c->d_tp_slot_range.ptr;
     v.range_slot = c->d_tp_range_slot.ptr; // (resolve_args names the MFMA route's maps)

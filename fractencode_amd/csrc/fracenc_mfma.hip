@@ -964,6 +964,11 @@ struct MfmaResolveArgs {
     // resolve_dft / resolve_small: per slot the search's own merge of its splits (search_dft with
     // DftArgs::slotbest, search_mfma with MfmaSearchArgs::slotbest), read in place of the entries and their CSR map
     const unsigned long long* slotbest = nullptr;
+    // resolve_dft<true> (the SEA tiled form): per block and lane the search's record (DftArgs::rec), each block's
+    // {group, wave} (none: group 0xffffffff, its record is never read) and the groups' windows {.., .., t0, t1}
+    const uint4* rec = nullptr;
+    const uint2* blk_group = nullptr;
+    const uint4* work = nullptr;
 };
 
 __device__ inline void apply_plan(MfmaResolveArgs& a)

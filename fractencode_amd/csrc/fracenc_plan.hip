@@ -117,9 +117,8 @@ constexpr uint32_t kTpKS = kDftTpForm == 4 ? 4u : 5u;                    // its 
 // it the route's fixed cost — two radix sorts, about ten small launches, one host turnaround — is too large a
 // share of the run to risk on unknown data (FRAC_FLAG_PRUNE ignores it).
 // kAutoPruneBudget: the share of those pairs the windows may hold; above it the windowed search with its exact
-// epilogue and per-chunk entries costs what the exhaustive search does, and the run falls back to that.  It
-// caps the entry arrays too: 128 bytes per pair of a full group, so at most the budget's share of the
-// worst case.
+// epilogue and its resolve costs what the exhaustive search does, and the run falls back to that.  (It bounds
+// time only: the windowed search's records are sized by the layout, not by the windows)
 // Measured (tools/auto_prune_sweep.py, profiles/r08/auto_prune/): a run forced to fall back costs 0.25 – 0.40 ms
 // more than the exhaustive one end to end — 13.5 % at 8.4 M pairs, 8.4 % at 16.7 M (4096², a quarter of the
 // ranges), 3.2 % at 66.9 M — so the 10 % line lies between the first two and the minimum sits just under the
@@ -467,7 +466,7 @@ int plan_tp_groups(frac_ctx* c, const PrepBuckets& B)
         bk.blk_count[b] = (bk.rng_count[b] + 31) / 32;
         nbk += bk.blk_count[b];
     }
-    if (nt >= (1u << 28)) // chunk entries hold the tile in 28 bits (search_dft CHUNKED)
+    if (nt >= (1u << 28)) // chunk words hold the tile in 28 bits (search_dft CHUNKED)
         return c->fail(FRAC_E_INVALID, "SEA: too many domain tiles");
     c->ntiles = nt;
     c->nblocks = nbk;
@@ -746,8 +745,9 @@ int fill_tp(frac_ctx* c, const PrepBuckets& B)
     // The tiled form's layout is ΣD4-sorted tiles and ΣR-sorted blocks, rebuilt every run; the MFMA route's is
     // the domain and range order, filled once (fill_mfma).  Under AUTO both stay prepared, so per buffer:
     //   own copy per layout — the maps and lists the MFMA route fills at prepare() and never again: tile_pos,
-    //     slot_range / range_slot, the 8-block work list and its block → entry CSR map (d_tp_* here, d_m_* /
-    //     d_m8_* there).  Small: 4 bytes per tile row, slot, range and entry link.
+    //     slot_range / range_slot, the 8-block work list (d_tp_* here), and the exhaustive route's block → entry
+    //     CSR map (d_m_* / d_m8_*; the tiled form has none: its search leaves one record per block and lane,
+    //     d_tp_rec).  Small: 4 bytes per tile row, slot and range, 16 per record.
     //   shared, rebuilt by whichever search runs — everything a run derives from the frame: the tile fragments
     //     and constants (d_m_dtiles, d_m_dconst), the guards, the tile-order pool copy (d_dft_tpool), the range
     //     fragments, constants and orbit copies (d_m_rfrags, d_m_rconst, d_dft_rorb) and d_m_entries.  dft_prep
@@ -766,14 +766,12 @@ int fill_tp(frac_ctx* c, const PrepBuckets& B)
     FRAC_HIP(c, c->d_dft_tpool.ensure(nt * 32 * 32));
     FRAC_HIP(c, c->d_dft_rguard.ensure(nbk));
     FRAC_HIP(c, c->d_tp_work.ensure(ng));
-    FRAC_HIP(c, c->d_tp_blk_ptr.ensure(nbk + 1));
+    FRAC_HIP(c, c->d_tp_rec.ensure(nbk * 64));
     FRAC_HIP(c, c->d_tp_sevals.ensure(ng));
     FRAC_HIP(c, c->d_tp_tile_sd.ensure(nt));
     FRAC_HIP(c, c->d_tp_row_of.ensure(P));
     FRAC_HIP(c, c->d_tp_blk_sr.ensure(nbk));
     FRAC_HIP(c, c->d_tp_blk_u.ensure(nbk));
-    FRAC_HIP(c, c->d_tp_nch.ensure(ng + 1));
-    FRAC_HIP(c, c->d_tp_choff.ensure(ng + 1));
     FRAC_HIP(c, c->h_tp_tot.ensure());
     FRAC_HIP(c, c->d_tp_sort_tmp.ensure(c->sea_tmp_bytes)); // (fill_sea ran: the larger of the sorts' needs)
     FRAC_HIP(c, c->d_tp_pairs.ensure(ng));
@@ -784,10 +782,6 @@ int fill_tp(frac_ctx* c, const PrepBuckets& B)
     if (nr)
         FRAC_HIP(c, hipMemcpyAsync(c->d_tp_rbk.ptr, c->d_rkey.ptr, nr * sizeof(int32_t), hipMemcpyDeviceToDevice,
                                    c->stream));
-    c->tp_iota.resize(ng);
-    for (size_t g = 0; g < ng; ++g)
-        c->tp_iota[g] = (uint32_t)g;
-    FRAC_TRY(upload(c, c->d_tp_iota, c->tp_iota));
     return FRAC_OK;
 }
 

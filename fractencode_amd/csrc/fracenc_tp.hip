@@ -11,10 +11,17 @@
 //   * then, in the same launch: per group the tiles whose ΣD4 interval meets [min ΣR − D, max ΣR + D],
 //     D² = n²·(max(U, H) + 1/2) over the group's ranges: outside it (ΣR − ΣD)²/n² alone
 //     exceeds the bound, so no candidate there can win, tie or hit (fracenc_sea.hip);
-//   * search_dft<…, CHUNKED> over each group's window, one entry per 4-tile chunk (the tiles
-//     are in ΣD4 order, not domain order, so every chunk attaining the maximum is kept and
-//     resolve_dft re-derives the least selection key over all of them: ties still go to the
-//     earliest domain, then the later transform).
+//   * search_dft<…, CHUNKED> over each group's window in 4-tile chunks.  The tiles are in ΣD4
+//     order, not domain order, so every chunk attaining a lane's maximum counts: the wave that
+//     holds a block sees all of its window's chunks and keeps, per lane, the maximum, how many
+//     chunks attain it and the first kTpRecList of them, one 16-byte record per lane
+//     (DftArgs::rec, nblocks·64 records: sized by the layout, not by the windows).  resolve_dft
+//     re-derives the least selection key over the listed chunks, or over the whole window when
+//     more attain the maximum than are listed: ties still go to the earliest domain, then the
+//     later transform.  The seed search is the same kernel over a one-tile window and writes
+//     the same records, which tp_seed_windows reads before the windowed search replaces them.
+// Nothing is sized from the windows; the host still waits once per run, for the totals
+// (frac_stats, and AUTO's budget test), which tp_plan sums into its pinned block.
 // Records are identical to the exhaustive search's; the cost is data-dependent.
 #include "fracenc_common.h"
 
@@ -282,16 +289,16 @@ __global__ void __launch_bounds__(256) tp_prep(MfmaDomainPrepArgs d, DftDomainBu
 // per block: the seed search's maximum y over the seed tile gives each slot U = 16Σa² − y, the
 // least exact error over that tile (exact regime; else no bound); the block's bound is the
 // greatest U over its slots (a 32-lane reduction, one writer per block)
-// (block `blk` is wave `k` of group `gi`'s seed workgroup; every lane of the 32-lane row returns the bound)
-__device__ __forceinline__ uint32_t tp_seed_reduce_row(uint32_t gi, uint32_t k, uint32_t blk, uint32_t col, bool live,
-                                                       const uint2* __restrict__ entries,
+// (every lane of the block's 32-lane row returns the bound)
+__device__ __forceinline__ uint32_t tp_seed_reduce_row(uint32_t blk, uint32_t col, bool live,
+                                                       const uint4* __restrict__ rec,
                                                        const int32_t* __restrict__ slot_range,
                                                        const uint32_t* __restrict__ rconst)
 {
     uint32_t u = 0u;
     if (live && slot_range[blk * 32u + col] >= 0) {
-        const size_t e = ((size_t)gi * 8u + k) * 64u + col;
-        const float y = fmaxf(__uint_as_float(entries[e].x), __uint_as_float(entries[e + 32].x));
+        const size_t e = (size_t)blk * 64u + col; // the slot's two row halves (search_dft CHUNKED)
+        const float y = fmaxf(__uint_as_float(rec[e].x), __uint_as_float(rec[e + 32].x));
         const int64_t sa16 = (int64_t)rconst[blk * 32u + col];
         // y = 16Σa² − min S16 is exact while min S16 < 2^24 (fracenc_dft.hip)
         u = y > (float)(sa16 - kExactLimit) ? (uint32_t)(sa16 - (int64_t)y) : 0xffffffffu;
@@ -302,44 +309,27 @@ __device__ __forceinline__ uint32_t tp_seed_reduce_row(uint32_t gi, uint32_t k, 
     return u;
 }
 
-// per group of ≤ 8 blocks: the tile window and its chunk count
+// per group of ≤ 8 blocks: the tile window
 struct TpWindowArgs {
     const uint4* groups;  // [ngroups] {first block, nblocks, tile_first, tile_count} (static)
     uint32_t ngroups;
     const uint2* blk_sr;
     uint32_t* blk_u;      // [nblocks] the seed bound of each block (written here)
-    const uint2* entries; // the seed search's entries, one chunk per group
+    const uint4* rec;     // the seed search's records, one per block and lane
     const int32_t* slot_range;
     const uint32_t* rconst;
     const uint2* tile_sd;
     int64_t hitH;         // −1: no hits
     uint4* work;          // [ngroups] {first block, nblocks, t0, t1}
-    uint32_t* nchunks;    // [ngroups]
     uint32_t* pairs;      // [ngroups] block × tile pairs searched (frac_stats.matrix_flops)
     TpBuckets bk;
     unsigned long long* evals; // [ngroups] (range, domain) pairs in the window (frac_stats.evaluated_mappings)
     unsigned long long* sevals; // [ngroups] (range, domain) pairs of the seed tile, read from work (tp_prep)
 };
 
-// tp_seed_windows: one workgroup per group.  Each 32-lane row reduces the seed search's entries of one block of
-// the group to its bound (tp_seed_reduce_row) and writes blk_u; one thread then sets the group's window.
-__global__ void __launch_bounds__(256) tp_seed_windows(TpWindowArgs a)
+// one group's window from its blocks' seed bounds (su), with the sums the totals are made of; one thread
+__device__ __forceinline__ void tp_seed_window_at(const TpWindowArgs& a, uint32_t gi, const uint4& gr, const uint32_t* su)
 {
-    __shared__ uint32_t su[kDftBlocksPerWG];
-    const uint32_t gi = blockIdx.x;
-    const uint4 gr = a.groups[gi];
-    {
-        const uint32_t k = threadIdx.x >> 5, col = threadIdx.x & 31u;
-        const bool live = k < gr.y;
-        const uint32_t bu = tp_seed_reduce_row(gi, k, gr.x + k, col, live, a.entries, a.slot_range, a.rconst);
-        if (live && col == 0) {
-            a.blk_u[gr.x + k] = bu;
-            su[k] = bu;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x != 0)
-        return;
     const uint32_t seed = a.work[gi].z; // the seed search's tile, before the window replaces it
     uint32_t srlo = 0xffffffffu, srhi = 0, u = 0;
     for (uint32_t k = 0; k < gr.y; ++k) {
@@ -374,7 +364,6 @@ __global__ void __launch_bounds__(256) tp_seed_windows(TpWindowArgs a)
         t1 = gr.z + max(a0, b0);
     }
     a.work[gi] = make_uint4(gr.x, gr.y, t0, t1);
-    a.nchunks[gi] = (t1 - t0 + 3) / 4;
     a.pairs[gi] = gr.y * (t1 - t0);
     // the (range, domain) pairs among them: the bucket's last block and last tile are partly padding
     uint32_t b = 0;
@@ -387,112 +376,45 @@ __global__ void __launch_bounds__(256) tp_seed_windows(TpWindowArgs a)
     a.sevals[gi] = (unsigned long long)slots * (min(s0 + 32u, a.bk.dom_count[b]) - s0);
 }
 
-// tp_plan: the entry arrays' layout and the totals the host needs, in one workgroup that walks its inputs in
-// passes of kTpPlanThreads with a carry:
-//   choff[0..ng]    the exclusive scan of the groups' chunk counts;
-//   blk_ptr[0..nbk] the exclusive scan of each block's entry count, its group's chunk count (none: 0);
-//   tot[0..8)       {chunks, block → entry links, Σ pairs (u64), Σ evals (u64), Σ seed evals (u64)}, written
-//                   straight into the host's pinned block (read after the stream synchronisation).
-constexpr uint32_t kTpPlanThreads = 256;
-
-// A pass alone is a chain of latencies (its loads, six shuffle steps, a barrier): kTpPlanAhead passes are taken
-// together, their loads and their in-wave scans side by side, under one barrier; the carry then runs through
-// their sums in registers.  (Eight measured best on a 4096² frame's 4 + 32 passes: one workgroup runs its code
-// once, from a cold instruction cache, and 32 unrolled passes cost more in code than they save in latency.)
-constexpr uint32_t kTpPlanAhead = 8;
-constexpr uint32_t kTpPlanWaves = kTpPlanThreads / 64;
-
-// the workgroup's exclusive scans of kTpPlanAhead passes, one value per thread and pass (0 past the input):
-// v[j] becomes the thread's offset in pass j, and the carry moves past them.  wsum: per pass one word per wave,
-// two sets taken in turn (`flip`), so one barrier per call is enough: a wave two calls ahead has crossed the
-// barrier that every reader of this set arrives at afterwards
-__device__ __forceinline__ void tp_plan_scan(uint32_t (&v)[kTpPlanAhead], uint32_t& carry,
-                                             uint32_t (*wsum)[kTpPlanAhead][kTpPlanWaves], uint32_t& flip)
+// tp_seed_windows: one workgroup per group.  Each 32-lane row reduces the seed search's records of one block of
+// the group to its bound (tp_seed_reduce_row) and writes blk_u; one thread then sets the group's window.
+__global__ void __launch_bounds__(256) tp_seed_windows(TpWindowArgs a)
 {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc[kTpPlanAhead];
-#pragma unroll
-    for (uint32_t j = 0; j < kTpPlanAhead; ++j)
-        inc[j] = v[j];
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1)
-#pragma unroll
-        for (uint32_t j = 0; j < kTpPlanAhead; ++j) {
-            const uint32_t t = (uint32_t)__shfl_up((int)inc[j], o, 64);
-            if (lane >= (uint32_t)o)
-                inc[j] += t;
+    __shared__ uint32_t su[kDftBlocksPerWG];
+    const uint32_t gi = blockIdx.x;
+    const uint4 gr = a.groups[gi];
+    {
+        const uint32_t k = threadIdx.x >> 5, col = threadIdx.x & 31u;
+        const bool live = k < gr.y;
+        const uint32_t bu = tp_seed_reduce_row(gr.x + k, col, live, a.rec, a.slot_range, a.rconst);
+        if (live && col == 0) {
+            a.blk_u[gr.x + k] = bu;
+            su[k] = bu;
         }
-    uint32_t(*ws)[kTpPlanWaves] = wsum[flip];
-    flip ^= 1u;
-    if (lane == 63u)
-#pragma unroll
-        for (uint32_t j = 0; j < kTpPlanAhead; ++j)
-            ws[j][wave] = inc[j];
-    __syncthreads();
-#pragma unroll
-    for (uint32_t j = 0; j < kTpPlanAhead; ++j) {
-        uint32_t before = 0, total = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < kTpPlanWaves; ++k) {
-            before += k < wave ? ws[j][k] : 0u;
-            total += ws[j][k];
-        }
-        v[j] = carry + before + inc[j] - v[j];
-        carry += total;
     }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        tp_seed_window_at(a, gi, gr, su);
 }
 
-__global__ void __launch_bounds__(kTpPlanThreads) tp_plan(const uint32_t* __restrict__ nchunks, uint32_t ngroups,
-                                                          const uint2* __restrict__ blk_group, uint32_t nblocks,
-                                                          const uint32_t* __restrict__ pairs,
+// tp_plan: the totals the host needs, in one workgroup: tot[0..8) = {0, 0, Σ pairs (u64), Σ evals (u64), Σ seed
+// evals (u64)} over the groups, written straight into the host's pinned block (read after the stream
+// synchronisation).  The first two words once held the chunk and entry-link counts; nothing is sized from the
+// windows now, and no scan is left.  (Summing them in tp_seed_windows' last workgroup instead — a device-scope
+// fence and a counter per group — saved the launch and measured 0.02 ms slower at C3: DESIGN §7.7.)
+constexpr uint32_t kTpPlanThreads = 256;
+
+__global__ void __launch_bounds__(kTpPlanThreads) tp_plan(uint32_t ngroups, const uint32_t* __restrict__ pairs,
                                                           const unsigned long long* __restrict__ evals,
                                                           const unsigned long long* __restrict__ sevals,
-                                                          uint32_t* __restrict__ choff, uint32_t* __restrict__ blk_ptr,
                                                           uint32_t* __restrict__ tot)
 {
-    __shared__ uint32_t wsum[2][kTpPlanAhead][kTpPlanWaves];
     __shared__ unsigned long long part[3][kTpPlanThreads / 64];
     unsigned long long s = 0, v = 0, q = 0;
-    uint32_t carry = 0, flip = 0;
-    // (uniform bounds: every thread takes every pass)
-    for (uint32_t g0 = 0; g0 < ngroups; g0 += kTpPlanAhead * kTpPlanThreads) {
-        uint32_t n[kTpPlanAhead];
-#pragma unroll
-        for (uint32_t j = 0; j < kTpPlanAhead; ++j) {
-            const uint32_t g = g0 + j * kTpPlanThreads + threadIdx.x;
-            n[j] = 0u;
-            if (g < ngroups) {
-                n[j] = nchunks[g];
-                s += pairs[g];
-                v += evals[g];
-                q += sevals[g];
-            }
-        }
-        tp_plan_scan(n, carry, wsum, flip);
-#pragma unroll
-        for (uint32_t j = 0; j < kTpPlanAhead; ++j) {
-            const uint32_t g = g0 + j * kTpPlanThreads + threadIdx.x;
-            if (g < ngroups)
-                choff[g] = n[j];
-        }
-    }
-    const uint32_t chunks = carry;
-    carry = 0;
-    for (uint32_t b0 = 0; b0 < nblocks; b0 += kTpPlanAhead * kTpPlanThreads) {
-        uint32_t n[kTpPlanAhead];
-#pragma unroll
-        for (uint32_t j = 0; j < kTpPlanAhead; ++j) {
-            const uint32_t b = b0 + j * kTpPlanThreads + threadIdx.x;
-            const uint32_t gi = b < nblocks ? blk_group[b].x : 0xffffffffu;
-            n[j] = gi == 0xffffffffu ? 0u : nchunks[gi];
-        }
-        tp_plan_scan(n, carry, wsum, flip);
-#pragma unroll
-        for (uint32_t j = 0; j < kTpPlanAhead; ++j) {
-            const uint32_t b = b0 + j * kTpPlanThreads + threadIdx.x;
-            if (b < nblocks)
-                blk_ptr[b] = n[j];
-        }
+    for (uint32_t g = threadIdx.x; g < ngroups; g += kTpPlanThreads) {
+        s += pairs[g];
+        v += evals[g];
+        q += sevals[g];
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -513,10 +435,8 @@ __global__ void __launch_bounds__(kTpPlanThreads) tp_plan(const uint32_t* __rest
             e += part[1][k];
             se += part[2][k];
         }
-        choff[ngroups] = chunks;
-        blk_ptr[nblocks] = carry;
-        tot[0] = chunks;
-        tot[1] = carry;
+        tot[0] = 0u;
+        tot[1] = 0u;
         tot[2] = (uint32_t)t;
         tot[3] = (uint32_t)(t >> 32);
         tot[4] = (uint32_t)e;
@@ -524,22 +444,6 @@ __global__ void __launch_bounds__(kTpPlanThreads) tp_plan(const uint32_t* __rest
         tot[6] = (uint32_t)se;
         tot[7] = (uint32_t)(se >> 32);
     }
-}
-
-// CSR block → entry bases ((chunk_offset[group] + c) · 8 + wave) read by resolve_dft
-__global__ void __launch_bounds__(256) tp_fill_entries(const uint2* __restrict__ blk_group,
-                                                       const uint32_t* __restrict__ choff,
-                                                       const uint32_t* __restrict__ blk_ptr, uint32_t nblocks,
-                                                       uint32_t* __restrict__ blk_ent)
-{
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= nblocks)
-        return;
-    const uint2 gw = blk_group[b];
-    if (gw.x == 0xffffffffu)
-        return;
-    for (uint32_t e = blk_ptr[b], c = 0; e < blk_ptr[b + 1]; ++e, ++c)
-        blk_ent[e] = (choff[gw.x] + c) * 8u + gw.y;
 }
 
 } // namespace fracenc
