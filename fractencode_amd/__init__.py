@@ -109,6 +109,16 @@ class FracFrc1Info(C.Structure):
                [(k, C.c_double) for k in ("contrast_min", "contrast_max", "brightness_min", "brightness_max")]
 
 
+class FracFrq1Info(C.Structure):
+    """struct frac_frq1_info: an FRQ1 header's fields, plus the per-level counts, widths and section offsets."""
+    _fields_ = [(k, C.c_uint32) for k in ("width", "height", "max_size", "min_size", "transforms", "contrast_bits",
+                                         "brightness_bits", "flags", "n_leaves", "levels")] + \
+               [(k, C.c_uint32 * 4) for k in ("nodes", "leaves", "n_domains", "index_bits", "record_bits")] + \
+               [(k, C.c_uint64 * 4) for k in ("bitmap_offset", "record_offset")] + \
+               [("body_bytes", C.c_uint64)] + \
+               [(k, C.c_double) for k in ("contrast_min", "contrast_max", "brightness_min", "brightness_max")]
+
+
 class FracError(RuntimeError):
     pass
 
@@ -204,6 +214,10 @@ def lib() -> C.CDLL:
             "frac_frc1_info": (i32, [vp, sz, C.POINTER(FracFrc1Info)]),
             "frac_decode_frc1": (i32, [vp, vp, sz, u32, i32, C.c_double, vp, sz, C.POINTER(C.c_int),
                                        C.POINTER(C.c_double)]),
+            "frac_frq1_info": (i32, [vp, sz, C.POINTER(FracFrq1Info)]),
+            "frac_pack_frq1": (i32, [vp, sz, u32, u32, u32, u32, u32, u32, u32, u32, vp, sz, C.POINTER(C.c_size_t)]),
+            "frac_decode_frq1": (i32, [vp, vp, sz, u32, i32, C.c_double, vp, sz, C.POINTER(C.c_int),
+                                       C.POINTER(C.c_double)]),
             "frac_fetch_tuples": (i32, [vp, vp]),
             "frac_decode": (i32, [vp, vp, sz, u32, u32, i32, C.c_double, vp, C.POINTER(C.c_int),
                                   C.POINTER(C.c_double)]),
@@ -283,6 +297,34 @@ def frc1_info(stream) -> dict:
     if lib().frac_frc1_info(buf.ctypes.data if len(buf) else None, len(buf), C.byref(out)) != 0:
         raise FracError(last_error())
     return {k: getattr(out, k) for k, _ in FracFrc1Info._fields_}
+
+
+def frq1_info(stream) -> dict:
+    """An FRQ1 stream's header and layout, validated against the stream's length on the host
+    (frac_frq1_info): the keys of codec.unpack_quadtree_stream's header dict without magic and version.
+    Raises FracError on a stream frac_decode_frq1 would refuse by its header or sections."""
+    buf = np.frombuffer(stream, dtype=np.uint8)
+    out = FracFrq1Info()
+    if lib().frac_frq1_info(buf.ctypes.data if len(buf) else None, len(buf), C.byref(out)) != 0:
+        raise FracError(last_error())
+    return {k: (list(getattr(out, k)) if hasattr(getattr(out, k), "__len__") else getattr(out, k))
+            for k, _ in FracFrq1Info._fields_}
+
+
+def pack_frq1(leaves: np.ndarray, width: int, height: int, max_size: int, min_size: int, transforms: int = 4,
+              use_classifier: bool = False, contrast_bits: int = 5, brightness_bits: int = 7) -> bytes:
+    """QT_LEAF leaves (encode_quadtree(leaves=True), its order) of a width×height frame as an FRQ1 stream
+    (codec.py layout), quantized and packed on the host in one pass (frac_pack_frq1)."""
+    leaves = np.ascontiguousarray(leaves, dtype=QT_LEAF)
+    args = (leaves.ctypes.data if len(leaves) else None, len(leaves), width, height, max_size, min_size, transforms,
+            1 if use_classifier else 0, contrast_bits, brightness_bits)
+    n = C.c_size_t(0)
+    if lib().frac_pack_frq1(*args, None, 0, C.byref(n)) != 0:
+        raise FracError(last_error())
+    buf = np.empty(n.value, dtype=np.uint8)
+    if lib().frac_pack_frq1(*args, buf.ctypes.data_as(C.c_void_p), n.value, C.byref(n)) != 0:
+        raise FracError(last_error())
+    return buf.tobytes()
 
 
 def transform_index(n: int, t: int, pix: int) -> int:
@@ -523,6 +565,33 @@ class Engine:
                                            plane.ctypes.data, plane.size, C.byref(it), C.byref(rms)))
         return plane, it.value, rms.value
 
+    def decode_frq1(self, stream, scale: int = 1, max_iter: int = -1, rms_eps: float = 1e-5,
+                    initial: np.ndarray | None = None):
+        """Decoder2::decode of an FRQ1 quadtree stream on the GPU (frac_decode_frq1): laid out, validated and
+        decoded on the device, every coordinate and size multiplied by `scale` (1..16).  `initial` as in
+        decode(), sized scale·H × scale·W.  Returns (plane, iterations, rms)."""
+        h = frq1_info(stream)
+        k = scale if 1 <= scale <= 16 else 0  # the library refuses the scale; no plane is sized by it
+        W, H = k * h["width"], k * h["height"]
+        plane = np.zeros((H, W), np.uint8) if initial is None else np.ascontiguousarray(initial, np.uint8).copy()
+        if plane.shape != (H, W):
+            raise FracError(f"decode_frq1: initial must be {H}x{W}")
+        buf = np.frombuffer(stream, dtype=np.uint8)
+        it = C.c_int()
+        rms = C.c_double()
+        self._check(lib().frac_decode_frq1(self._ctx, buf.ctypes.data, len(buf), scale, max_iter, rms_eps,
+                                           plane.ctypes.data, plane.size, C.byref(it), C.byref(rms)))
+        return plane, it.value, rms.value
+
+    def encode_quadtree_stream(self, max_size: int = 16, min_size: int = 4, split_distance: float = 10.0,
+                               contrast_bits: int = 5, brightness_bits: int = 7):
+        """The quadtree partition of the frame set on this engine as an FRQ1 stream: encode_quadtree(leaves=True)
+        and pack_frq1 with the engine's transforms and classifier flag.  Returns (bytes, summed stats dict)."""
+        leaves, st = self.encode_quadtree(max_size, min_size, split_distance, leaves=True)
+        W, H = self._frame_wh
+        return pack_frq1(leaves, W, H, max_size, min_size, self._p.transforms, bool(self._p.use_classifier),
+                         contrast_bits, brightness_bits), st
+
     def encode_quadtree(self, max_size: int = 16, min_size: int = 4, split_distance: float = 10.0, out=None,
                         allow_short: bool = False, leaves: bool = False):
         """Quadtree partition of the frame set on this engine (frac_encode_quadtree): ranges of
@@ -626,7 +695,10 @@ def encode(plane: np.ndarray, range_size: int = 4, domain_size: int = 16, transf
 
 
 def decode_stream(stream, scale: int = 1, device: int = 0, **kw):
-    """One call from an FRC1 stream to pixels, beside encode(): Engine.decode_frc1 on a context of its own
-    (kw: max_iter, rms_eps, initial).  Returns (plane, iterations, rms)."""
+    """One call from a stream to pixels, beside encode(): Engine.decode_frc1, or Engine.decode_frq1 for a stream
+    whose magic is FRQ1, on a context of its own (kw: max_iter, rms_eps, initial).  Returns (plane, iterations,
+    rms)."""
     with Engine(device) as e:
+        if bytes(memoryview(stream)[:4]) == b"FRQ1":
+            return e.decode_frq1(stream, scale, **kw)
         return e.decode_frc1(stream, scale, **kw)

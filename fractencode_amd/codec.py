@@ -31,6 +31,35 @@ When every value of a field is equal the quantizer would be degenerate (the refe
 asserts max > min, Quantizer.hpp:19): the header then stores min == max and every
 record dequantizes to exactly that value.
 frac_decode_frc1 (Engine.decode_frc1) consumes this layout on the device; unpack_stream is its host restatement.
+
+Quadtree stream layout ("FRQ1", little-endian): the leaves of frac_encode_quadtree, whose sizes differ, so
+the partition itself is part of the stream::
+
+    0   char[4]  magic "FRQ1"
+    4   u16      version (1)
+    6   u16      flags (bit 0: classifier was on; informational)
+    8   u32      width, height
+    16  u8       max_size, min_size, transforms, contrast_bits, brightness_bits, then three zero bytes
+    24  u32      n_leaves, then one zero u32
+    32  f64      contrast_min, contrast_max, brightness_min, brightness_max
+    64  body
+
+Levels are k = 0..L−1 with sides n_k = max_size >> k down to min_size (sides from {2, 4, 8, 16}, L ≤ 4).
+The nodes of level 0 are createUniformGrid(max_size, max_size) in row-major order; the nodes of level k+1
+are, for each split node of level k in that level's order, its quadrants top-left, top-right, bottom-left,
+bottom-right (N_{k+1} = 4·S_k).  This is the order frac_encode_quadtree emits its leaves in.  The body holds,
+per level in level order:
+
+    split bitmap  for k < L−1 only: N_k bits, LSB first, 1 = split; zero-padded to a whole dword (the
+                  padding bits must be 0); no bytes when N_k = 0
+    records       the level's M_k = N_k − S_k leaves in node order (the last level has no bitmap: every
+                  node is a leaf): (domain index, transform, q_contrast, q_brightness) bit-packed LSB first
+                  exactly as FRC1, index_bits_k = max(1, bitlen(nd_k)) wide with nd_k the count of
+                  createUniformGrid(2·n_k, n_k); index == nd_k: no domain; zero-padded to a whole dword
+
+One quantizer pair covers the whole stream, built over every leaf's contrast and brightness as FRC1's.
+frac_decode_frq1 (Engine.decode_frq1) consumes this layout on the device, frac_pack_frq1 writes it from
+32-byte leaves; pack_quadtree_stream / unpack_quadtree_stream are the host restatement.
 """
 from __future__ import annotations
 
@@ -238,3 +267,182 @@ def unpack_stream(buf: bytes) -> tuple[np.ndarray, dict]:
     out["brightness"] = np.where(has, deq(qo, h["brightness_min"], h["brightness_max"], h["brightness_bits"]), 0.0)
     out["transform"] = np.where(has, out["transform"], 0)
     return out, h
+
+
+# ---- FRQ1: the quadtree stream (layout in the module docstring) ---------------------------------
+
+QT_MAGIC = b"FRQ1"
+QT_HEADER = struct.Struct("<4sHHIIBBBBB3xIIdddd")
+assert QT_HEADER.size == 64
+QT_SIZES = (2, 4, 8, 16)
+
+
+def quadtree_levels(max_size: int, min_size: int) -> list[int]:
+    """The level sides max_size, max_size / 2, …, min_size."""
+    if max_size not in QT_SIZES or min_size not in QT_SIZES or min_size > max_size:
+        raise ValueError("FRQ1: sizes must be 2, 4, 8 or 16, min_size at most max_size")
+    out = [max_size]
+    while out[-1] > min_size:
+        out.append(out[-1] // 2)
+    return out
+
+
+def _level0_nodes(width: int, height: int, n: int) -> tuple[np.ndarray, np.ndarray]:
+    rc, rr = _grid_cols_rows(width, height, n, n)
+    r = np.arange(rc * rr, dtype=np.int64)
+    return (r % max(rc, 1)) * n, (r // max(rc, 1)) * n
+
+
+def _children(x: np.ndarray, y: np.ndarray, n: int) -> tuple[np.ndarray, np.ndarray]:
+    """The quadrants (top-left, top-right, bottom-left, bottom-right) of the nodes, node by node."""
+    h = n // 2
+    return ((x[:, None] + np.array([0, h, 0, h])).reshape(-1), (y[:, None] + np.array([0, 0, h, h])).reshape(-1))
+
+
+def _pad4(b: bytes) -> bytes:
+    return b + bytes(-len(b) % 4)
+
+
+def pack_quadtree_stream(items: np.ndarray, width: int, height: int, max_size: int, min_size: int,
+                         transforms: int = 4, use_classifier: bool = False, contrast_bits: int = CONTRAST_BITS,
+                         brightness_bits: int = BRIGHTNESS_BITS) -> bytes:
+    """Quantize and pack quadtree leaves (ENCODE_ITEM records in frac_encode_quadtree's output order) into FRQ1."""
+    from . import ENCODE_ITEM
+
+    items = np.ascontiguousarray(items, dtype=ENCODE_ITEM)
+    sizes = quadtree_levels(max_size, min_size)
+    if not (0 < width <= 65535 and 0 < height <= 65535):
+        raise ValueError("FRQ1: width and height must be in 1..65535")
+    if np.any(items["w"] != items["h"]) or not np.isin(items["w"], sizes).all():
+        raise ValueError("pack_quadtree_stream: a leaf's size is none of the levels'")
+    if len(items) > 1 and np.any(np.diff(items["w"].astype(np.int64)) > 0):
+        raise ValueError("pack_quadtree_stream: leaves are not in level order")
+    s_f = _Field(items["contrast"], contrast_bits)
+    o_f = _Field(items["brightness"], brightness_bits)
+    t_bits = max(1, int(transforms - 1).bit_length())
+    if len(items) and int(items["transform"].max()) >= transforms or len(items) and int(items["transform"].min()) < 0:
+        raise ValueError("pack_quadtree_stream: a transform outside the stream's")
+    body = b""
+    x, y = _level0_nodes(width, height, sizes[0])
+    for k, n in enumerate(sizes):
+        lv = items[items["w"] == n]
+        key, lkey = y * 65536 + x, lv["y"].astype(np.int64) * 65536 + lv["x"]
+        leaf = np.isin(key, lkey)
+        if int(leaf.sum()) != len(lv) or np.any(key[leaf] != lkey):
+            raise ValueError(f"pack_quadtree_stream: the {n}-level's leaves are not its nodes in canonical order")
+        if k + 1 < len(sizes):
+            body += _pad4(np.packbits((~leaf).astype(np.uint8), bitorder="little").tobytes())
+        elif not leaf.all():
+            raise ValueError("pack_quadtree_stream: a node of the last level has no leaf")
+        dc, dr = _grid_cols_rows(width, height, 2 * n, n)
+        nd = dc * dr
+        has = (lv["sw"] != 0) & (lv["sh"] != 0)
+        if np.any(has & ((lv["sw"] != 2 * n) | (lv["sh"] != 2 * n) | (lv["dx"] % n != 0) | (lv["dy"] % n != 0))):
+            raise ValueError("pack_quadtree_stream: a winner is not on its level's domain lattice")
+        idx = np.where(has, (lv["dy"] // n).astype(np.int64) * dc + lv["dx"] // n, nd).astype(np.uint64)
+        if np.any(has & ((idx >= nd) | (lv["dx"] // n >= max(dc, 1)))):
+            raise ValueError("pack_quadtree_stream: a winner lies outside its level's domain grid")
+        body += _pad4(_pack_bits([(idx, max(1, int(nd).bit_length())), (lv["transform"].astype(np.uint64), t_bits),
+                                  (s_f.codes(lv["contrast"]), contrast_bits),
+                                  (o_f.codes(lv["brightness"]), brightness_bits)], len(lv)))
+        x, y = _children(x[~leaf], y[~leaf], n)
+    hdr = QT_HEADER.pack(QT_MAGIC, VERSION, 1 if use_classifier else 0, width, height, max_size, min_size, transforms,
+                         contrast_bits, brightness_bits, len(items), 0, s_f.min, s_f.max, o_f.min, o_f.max)
+    return hdr + body
+
+
+def read_quadtree_header(buf: bytes) -> dict:
+    if len(buf) < QT_HEADER.size:
+        raise ValueError("FRQ1: truncated header")
+    f = QT_HEADER.unpack_from(buf, 0)
+    if f[0] != QT_MAGIC or f[1] != VERSION:
+        raise ValueError("FRQ1: bad magic or version")
+    keys = ("magic", "version", "flags", "width", "height", "max_size", "min_size", "transforms", "contrast_bits",
+            "brightness_bits", "n_leaves", "reserved", "contrast_min", "contrast_max", "brightness_min",
+            "brightness_max")
+    h = dict(zip(keys, f))
+    if h.pop("reserved") or any(buf[21:24]):
+        raise ValueError("FRQ1: a reserved byte or word is not zero")
+    if not (0 < h["width"] <= 65535 and 0 < h["height"] <= 65535):
+        raise ValueError("FRQ1: width and height must be in 1..65535")
+    quadtree_levels(h["max_size"], h["min_size"])
+    if not 1 <= h["transforms"] <= 8:
+        raise ValueError("FRQ1: transforms outside 1..8")
+    if not (2 <= h["contrast_bits"] <= 24 and 2 <= h["brightness_bits"] <= 24):
+        raise ValueError("FRQ1: contrast / brightness bits outside [2, 24]")
+    if not all(np.isfinite(h[k]) for k in ("contrast_min", "contrast_max", "brightness_min", "brightness_max")):
+        raise ValueError("FRQ1: non-finite quantizer bound")
+    return h
+
+
+def unpack_quadtree_stream(buf: bytes) -> tuple[np.ndarray, dict]:
+    """FRQ1 → (encode_item_t records in the stream's order with dequantized contrast/brightness, header dict).
+    The dict also carries what the walk derives: levels and, per level, nodes, leaves, n_domains, index_bits,
+    record_bits, bitmap_offset and record_offset (bytes from the start of the stream), and body_bytes.
+    `distance` is not carried by the stream and comes back as 0."""
+    from . import ENCODE_ITEM
+
+    buf = bytes(buf)
+    h = read_quadtree_header(buf)
+    sizes = quadtree_levels(h["max_size"], h["min_size"])
+    W, H = h["width"], h["height"]
+    t_bits = max(1, int(h["transforms"] - 1).bit_length())
+    for k in ("nodes", "leaves", "n_domains", "index_bits", "record_bits", "bitmap_offset", "record_offset"):
+        h[k] = [0] * 4
+    h["levels"] = len(sizes)
+    parts = []
+    pos = QT_HEADER.size
+    x, y = _level0_nodes(W, H, sizes[0])
+    for k, n in enumerate(sizes):
+        N = len(x)
+        split = np.zeros(N, dtype=bool)
+        h["bitmap_offset"][k] = pos
+        if k + 1 < len(sizes):
+            nb = (N + 31) // 32 * 4
+            if len(buf) < pos + nb:
+                raise ValueError("FRQ1: truncated split bitmap")
+            bits = np.unpackbits(np.frombuffer(buf, np.uint8, nb, pos), bitorder="little")
+            if bits[N:].any():
+                raise ValueError("FRQ1: a padding bit of a split bitmap is set")
+            split = bits[:N].astype(bool)
+            pos += nb
+        dc, dr = _grid_cols_rows(W, H, 2 * n, n)
+        nd = dc * dr
+        widths = [max(1, int(nd).bit_length()), t_bits, h["contrast_bits"], h["brightness_bits"]]
+        M = N - int(split.sum())
+        nb = (M * sum(widths) + 31) // 32 * 4
+        if len(buf) < pos + nb:
+            raise ValueError("FRQ1: truncated records")
+        h["nodes"][k], h["leaves"][k], h["n_domains"][k] = N, M, nd
+        h["index_bits"][k], h["record_bits"][k], h["record_offset"][k] = widths[0], sum(widths), pos
+        idx, t, qs, qo = _unpack_bits(buf[pos:pos + nb], M, widths)
+        pos += nb
+        if np.any(idx > nd):
+            raise ValueError("FRQ1: domain index out of range")
+        out = np.zeros(M, dtype=ENCODE_ITEM)
+        out["x"], out["y"] = x[~split], y[~split]
+        out["w"] = out["h"] = n
+        has = idx < nd
+        di = np.where(has, idx, 0).astype(np.int64)
+        out["dx"] = np.where(has, (di % max(dc, 1)) * n, 0)
+        out["dy"] = np.where(has, (di // max(dc, 1)) * n, 0)
+        out["sw"] = out["sh"] = np.where(has, 2 * n, 0)
+        out["transform"] = np.where(has, t.astype(np.int32), 0)
+        parts.append((out, has, qs, qo))
+        x, y = _children(x[split], y[split], n)
+    h["body_bytes"] = pos - QT_HEADER.size
+    rec = np.concatenate([p[0] for p in parts])
+    if len(rec) != h["n_leaves"]:
+        raise ValueError("FRQ1: n_leaves is not the levels' leaf count")
+    has = np.concatenate([p[1] for p in parts])
+
+    def deq(codes, lo, hi, bits):
+        if not hi > lo:
+            return np.full(len(rec), lo)
+        return Quantizer(lo, hi, bits).value(codes)
+
+    rec["contrast"] = np.where(has, deq(np.concatenate([p[2] for p in parts]), h["contrast_min"], h["contrast_max"],
+                                        h["contrast_bits"]), 0.0)
+    rec["brightness"] = np.where(has, deq(np.concatenate([p[3] for p in parts]), h["brightness_min"],
+                                          h["brightness_max"], h["brightness_bits"]), 0.0)
+    return rec, h

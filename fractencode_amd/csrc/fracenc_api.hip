@@ -5,7 +5,7 @@
 //   fracenc_plan.hip     validation, device bucketing, prepare(): work lists and buffers per engine
 //   fracenc_launch.hip   variant selection, the engines' launch paths, the fp32 fallback
 //   fracenc_quadtree.hip quadtree frames, host- and device-planned
-//   fracenc_codec.hip    decode, FRC1 pack / parse / decode, colour conversion
+//   fracenc_codec.hip    decode, FRC1 and FRQ1 pack / parse / decode, colour conversion
 //
 // Host logic mirrored from the reference:
 //   classifier gating      encode/Classifier2.cpp:8-81   (categories computed on the host,
@@ -33,6 +33,7 @@
 #include "fracenc_sea.hip"
 #include "fracenc_stream.hip"
 #include "fracenc_frc1dec.hip"
+#include "fracenc_frq1dec.hip"
 #include "fracenc_tp.hip"
 #include "fracenc_gen.hip"
 #include "fracenc_bucket.hip"

@@ -544,4 +544,389 @@ int frac_decode_frc1(frac_ctx* c, const uint8_t* stream, size_t len, uint32_t sc
     return decode_impl(c, c->d_dec_items.ptr, n, W, H, max_iter, rms_eps, plane, iterations, rms, tiles);
 }
 
+// ---- FRQ1: the quadtree stream (fractencode_amd/codec.py documents the layout) -------------------
+
+static uint32_t frq1_bitlen(uint64_t v)
+{
+    uint32_t b = 0;
+    while (v) {
+        ++b;
+        v >>= 1;
+    }
+    return b;
+}
+
+// the level sides max, max / 2, …, min into n[]; 0 when the sizes are not the format's
+static uint32_t frq1_levels(uint32_t max_size, uint32_t min_size, uint32_t n[4])
+{
+    auto ok = [](uint32_t s) { return s == 2 || s == 4 || s == 8 || s == 16; };
+    if (!ok(max_size) || !ok(min_size) || min_size > max_size)
+        return 0;
+    uint32_t L = 0;
+    for (uint32_t s = max_size; s >= min_size; s >>= 1)
+        n[L++] = s;
+    return L;
+}
+
+// The FRQ1 header "<4sHHIIBBBBB3xIIdddd" parsed, the bitmaps walked, everything checked against the stream
+// length; on failure `msg` names the rule.
+using Frq1Info = struct frac_frq1_info; // the plain name is the function's
+static int frq1_parse(const uint8_t* s, size_t len, Frq1Info* o, std::string& msg)
+{
+    auto bad = [&](const char* why) {
+        msg = std::string("FRQ1: ") + why;
+        return FRAC_E_INVALID;
+    };
+    if (!s || !o)
+        return bad("NULL argument");
+    if (len < FRAC_FRQ1_HEADER_BYTES)
+        return bad("truncated header");
+    uint16_t version, flags;
+    uint32_t wh[2], counts[2];
+    double mm[4];
+    std::memcpy(&version, s + 4, 2);
+    std::memcpy(&flags, s + 6, 2);
+    std::memcpy(wh, s + 8, sizeof(wh));
+    std::memcpy(counts, s + 24, sizeof(counts));
+    std::memcpy(mm, s + 32, sizeof(mm));
+    if (std::memcmp(s, "FRQ1", 4) != 0 || version != 1)
+        return bad("bad magic or version");
+    *o = Frq1Info{};
+    o->width = wh[0], o->height = wh[1], o->max_size = s[16], o->min_size = s[17];
+    o->transforms = s[18], o->contrast_bits = s[19], o->brightness_bits = s[20], o->flags = flags;
+    o->n_leaves = counts[0];
+    o->contrast_min = mm[0], o->contrast_max = mm[1], o->brightness_min = mm[2], o->brightness_max = mm[3];
+    if (o->width == 0 || o->height == 0 || o->width > 65535 || o->height > 65535)
+        return bad("width and height must be in 1..65535");
+    uint32_t side[4];
+    o->levels = frq1_levels(o->max_size, o->min_size, side);
+    if (!o->levels)
+        return bad("sizes must be 2, 4, 8 or 16, min_size at most max_size");
+    if (o->transforms < 1 || o->transforms > 8)
+        return bad("transforms outside 1..8");
+    if (o->contrast_bits < 2 || o->contrast_bits > 24 || o->brightness_bits < 2 || o->brightness_bits > 24)
+        return bad("contrast / brightness bits outside [2, 24]");
+    if (s[21] || s[22] || s[23] || counts[1])
+        return bad("a reserved byte or word is not zero");
+    const uint32_t t_bits = std::max(1u, frq1_bitlen(o->transforms - 1));
+    for (uint32_t k = 0; k < o->levels; ++k) {
+        o->n_domains[k] = (uint32_t)frac_uniform_grid(o->width, o->height, 2 * side[k], side[k], nullptr, 0);
+        o->index_bits[k] = std::max(1u, frq1_bitlen(o->n_domains[k]));
+        o->record_bits[k] = o->index_bits[k] + t_bits + o->contrast_bits + o->brightness_bits;
+        if (o->record_bits[k] > 64)
+            return bad("record wider than 64 bits");
+    }
+    uint64_t pos = FRAC_FRQ1_HEADER_BYTES, total = 0;
+    uint64_t N = frac_uniform_grid(o->width, o->height, o->max_size, o->max_size, nullptr, 0);
+    for (uint32_t k = 0; k < o->levels; ++k) {
+        uint64_t S = 0;
+        o->bitmap_offset[k] = pos;
+        if (k + 1 < o->levels) {
+            const uint64_t nw = (N + 31) / 32;
+            if (len - pos < nw * 4)
+                return bad("the stream ends inside a split bitmap");
+            for (uint64_t j = 0; j < nw; ++j) {
+                uint32_t w;
+                std::memcpy(&w, s + pos + 4 * j, 4);
+                if (j == nw - 1 && (N & 31u) && (w >> (N & 31u)))
+                    return bad("a padding bit of a split bitmap is set");
+                S += (uint32_t)__builtin_popcount(w);
+            }
+            pos += nw * 4;
+        }
+        const uint64_t M = N - S, nb = (M * o->record_bits[k] + 31) / 32 * 4;
+        if (len - pos < nb)
+            return bad("the stream ends inside a record section");
+        o->nodes[k] = (uint32_t)N, o->leaves[k] = (uint32_t)M, o->record_offset[k] = pos;
+        pos += nb;
+        total += M;
+        N = 4 * S;
+    }
+    o->body_bytes = pos - FRAC_FRQ1_HEADER_BYTES;
+    if (total != o->n_leaves)
+        return bad("n_leaves is not the levels' leaf count");
+    for (double v : mm)
+        if (!std::isfinite(v))
+            return bad("non-finite quantizer bound");
+    return FRAC_OK;
+}
+
+int frac_frq1_info(const uint8_t* stream, size_t len, struct frac_frq1_info* out)
+{
+    std::string msg;
+    const int rc = frq1_parse(stream, len, out, msg);
+    if (rc != FRAC_OK)
+        g_last_error = msg;
+    return rc;
+}
+
+int frac_pack_frq1(const frac_qt_leaf* leaves, size_t n, uint32_t W, uint32_t H, uint32_t max_size, uint32_t min_size,
+                   uint32_t T, uint32_t stream_flags, uint32_t cbits, uint32_t bbits, uint8_t* out, size_t cap,
+                   size_t* n_out)
+{
+    auto bad = [&](const std::string& why) {
+        g_last_error = "pack_frq1: " + why;
+        return FRAC_E_INVALID;
+    };
+    if (!n_out || (n && !leaves))
+        return bad("NULL argument");
+    if (cbits < 2 || cbits > 16 || bbits < 2 || bbits > 16)
+        return bad("contrast/brightness bits must be in [2, 16]");
+    if (W == 0 || H == 0 || W > 65535 || H > 65535)
+        return bad("width and height must be in 1..65535");
+    uint32_t side[4];
+    const uint32_t L = frq1_levels(max_size, min_size, side);
+    if (!L)
+        return bad("sizes must be 2, 4, 8 or 16, min_size at most max_size");
+    if (T < 1 || T > 8)
+        return bad("transforms outside 1..8");
+    // one quantizer pair over every leaf (codec._Field): min and max, the degenerate field coded as 0
+    double cmin = 0.0, cmax = 0.0, bmin = 0.0, bmax = 0.0;
+    for (size_t i = 0; i < n; ++i) {
+        const double cv = leaves[i].contrast, bv = leaves[i].brightness;
+        if (!std::isfinite(cv) || !std::isfinite(bv))
+            return bad("leaf " + std::to_string(i) + ": non-finite contrast or brightness");
+        cmin = i ? std::min(cmin, cv) : cv, cmax = i ? std::max(cmax, cv) : cv;
+        bmin = i ? std::min(bmin, bv) : bv, bmax = i ? std::max(bmax, bv) : bv;
+    }
+    // Frac::Quantizer::quantized in FP64 (codec.Quantizer.quantized)
+    auto quant = [](double v, double lo, double hi, uint32_t bits) -> uint64_t {
+        if (!(hi > lo))
+            return 0;
+        const double step = std::fabs(hi - lo) / (double)(1u << bits);
+        const double q = std::floor((v - lo) / step), qmax = (double)((1u << bits) - 1u);
+        return (uint64_t)(q < qmax ? q : qmax);
+    };
+    const uint32_t tb = std::max(1u, frq1_bitlen(T - 1));
+    std::vector<uint32_t> body, nodes, next;
+    // level 0: createUniformGrid(max, max), row-major
+    {
+        const size_t cnt = frac_uniform_grid(W, H, max_size, max_size, nullptr, 0);
+        const uint32_t cols = cnt ? (W - max_size) / max_size + 1 : 0;
+        nodes.resize(cnt);
+        for (size_t i = 0; i < cnt; ++i)
+            nodes[i] = (uint32_t)(i % cols) * max_size | ((uint32_t)(i / cols) * max_size) << 16;
+    }
+    size_t p = 0; // the next leaf
+    for (uint32_t k = 0; k < L; ++k) {
+        const uint32_t sz = side[k], lg = frq1_bitlen(sz) - 1;
+        const uint64_t nd = frac_uniform_grid(W, H, 2 * sz, sz, nullptr, 0);
+        const uint32_t ib = std::max(1u, frq1_bitlen(nd)), width = ib + tb + cbits + bbits;
+        if (width > 64)
+            return bad("record wider than 64 bits");
+        const bool last = k + 1 == L;
+        const size_t bm = body.size();
+        if (!last)
+            body.resize(bm + (nodes.size() + 31) / 32, 0u);
+        std::vector<uint32_t> recs; // the level's record section, filled bit by bit
+        uint64_t bit = 0;
+        next.clear();
+        for (size_t i = 0; i < nodes.size(); ++i) {
+            const uint32_t x = nodes[i] & 0xffffu, y = nodes[i] >> 16;
+            const bool leaf = p < n && (leaves[p].code >> 28) == lg && leaves[p].x == x && leaves[p].y == y;
+            if (!leaf) {
+                if (last)
+                    return bad("leaf " + std::to_string(p) + " is not the next leaf of the canonical order (the node at (" +
+                               std::to_string(x) + ", " + std::to_string(y) + ") of the last level has none)");
+                body[bm + (i >> 5)] |= 1u << (i & 31u);
+                const uint32_t h = sz / 2;
+                next.push_back(x | y << 16);
+                next.push_back((x + h) | y << 16);
+                next.push_back(x | (y + h) << 16);
+                next.push_back((x + h) | (y + h) << 16);
+                continue;
+            }
+            const frac_qt_leaf& e = leaves[p];
+            const uint32_t d = e.code & FRAC_QT_NO_DOMAIN, t = (e.code >> 24) & 15u;
+            if (d != FRAC_QT_NO_DOMAIN && d >= nd)
+                return bad("leaf " + std::to_string(p) + ": domain index outside its level's grid");
+            if (t >= T)
+                return bad("leaf " + std::to_string(p) + ": transform outside the stream's");
+            const uint64_t rec = (d == FRAC_QT_NO_DOMAIN ? nd : (uint64_t)d) | (uint64_t)t << ib |
+                                 quant(e.contrast, cmin, cmax, cbits) << (ib + tb) |
+                                 quant(e.brightness, bmin, bmax, bbits) << (ib + tb + cbits);
+            recs.resize((size_t)((bit + width + 31) / 32), 0u);
+            const uint32_t sh = (uint32_t)(bit & 31u);
+            const size_t w = (size_t)(bit >> 5);
+            recs[w] |= (uint32_t)(rec << sh);
+            if (sh + width > 32)
+                recs[w + 1] |= (uint32_t)(rec >> (32 - sh));
+            if (sh + width > 64)
+                recs[w + 2] |= (uint32_t)(rec >> (64 - sh));
+            bit += width;
+            ++p;
+        }
+        // a leaf of this level still next: it is no node of the level, or out of order, or there twice
+        if (p < n && (leaves[p].code >> 28) >= lg)
+            return bad("leaf " + std::to_string(p) + " is not the next leaf of the canonical order");
+        body.insert(body.end(), recs.begin(), recs.end());
+        nodes.swap(next);
+    }
+    if (p != n)
+        return bad("leaf " + std::to_string(p) + " is not the next leaf of the canonical order");
+    const size_t total = FRAC_FRQ1_HEADER_BYTES + body.size() * 4;
+    *n_out = total;
+    if (!out)
+        return FRAC_OK;
+    uint8_t hdr[FRAC_FRQ1_HEADER_BYTES] = {};
+    const uint16_t version = 1, flags = (uint16_t)stream_flags;
+    const uint32_t wh[2] = {W, H}, nl = (uint32_t)n;
+    const uint8_t u8s[5] = {(uint8_t)max_size, (uint8_t)min_size, (uint8_t)T, (uint8_t)cbits, (uint8_t)bbits};
+    const double mm[4] = {cmin, cmax, bmin, bmax};
+    std::memcpy(hdr, "FRQ1", 4);
+    std::memcpy(hdr + 4, &version, 2);
+    std::memcpy(hdr + 6, &flags, 2);
+    std::memcpy(hdr + 8, wh, 8);
+    std::memcpy(hdr + 16, u8s, 5);
+    std::memcpy(hdr + 24, &nl, 4);
+    std::memcpy(hdr + 32, mm, 32);
+    std::memcpy(out, hdr, std::min<size_t>(cap, FRAC_FRQ1_HEADER_BYTES));
+    if (cap > FRAC_FRQ1_HEADER_BYTES && !body.empty())
+        std::memcpy(out + FRAC_FRQ1_HEADER_BYTES, body.data(), std::min(cap, total) - FRAC_FRQ1_HEADER_BYTES);
+    return FRAC_OK;
+}
+
+int frac_decode_frq1(frac_ctx* c, const uint8_t* stream, size_t len, uint32_t scale, int max_iter, double rms_eps,
+                     uint8_t* plane, size_t plane_bytes, int* iterations, double* rms)
+{
+    if (!c)
+        return FRAC_E_INVALID;
+    Frq1Info h;
+    {
+        std::string msg;
+        if (frq1_parse(stream, len, &h, msg) != FRAC_OK)
+            return c->fail(FRAC_E_INVALID, msg);
+    }
+    FRAC_TRY(check_ab_knobs(c));
+    if (scale < 1 || scale > 16 || (uint64_t)scale * h.width > 65535 || (uint64_t)scale * h.height > 65535)
+        return c->fail(FRAC_E_INVALID, "decode_frq1: scale must be in 1..16 and the scaled frame at most 65535 a side");
+    const uint32_t W = scale * h.width, H = scale * h.height;
+    if (!plane || plane_bytes < (uint64_t)W * H)
+        return c->fail(FRAC_E_INVALID, "decode_frq1: the plane is smaller than the scaled frame");
+    for (uint32_t k = 0; k < h.levels; ++k)
+        if (h.n_domains[k] >= (1u << 24))
+            return c->fail(FRAC_E_INVALID, "decode_frq1: a level with 2^24 or more domains");
+    const uint32_t n = h.n_leaves;
+    Frq1Layout L{};
+    L.n_leaves = n;
+    L.dc1 = L.dc2 = L.dc3 = L.dc4 = 1;
+    for (uint32_t k = 0; k < h.levels; ++k) {
+        const uint32_t sz = h.max_size >> k, nd = h.n_domains[k];
+        const uint32_t dc = nd ? (h.width - 2 * sz) / sz + 1 : 1;
+        (sz == 2 ? L.dc1 : sz == 4 ? L.dc2 : sz == 8 ? L.dc3 : L.dc4) = dc;
+        (sz == 2 ? L.nd1 : sz == 4 ? L.nd2 : sz == 8 ? L.nd3 : L.nd4) = nd;
+    }
+    // Quantizer (encode/Quantizer.hpp:19-22): step = |max − min| / 2^bits; !(max > min): every code is min
+    auto step = [](double lo, double hi, uint32_t bits) {
+        return hi > lo ? std::fabs(hi - lo) / (double)(1u << bits) : 0.0;
+    };
+    L.c_step = step(h.contrast_min, h.contrast_max, h.contrast_bits);
+    L.c_min = h.contrast_min;
+    L.b_step = step(h.brightness_min, h.brightness_max, h.brightness_bits);
+    L.b_min = h.brightness_min;
+
+    FRAC_HIP(c, hipSetDevice(c->device));
+    // the fast path's geometry: the level-0 grid covers the frame, so the leaves tile it
+    const bool tiles = n && h.width % h.max_size == 0 && h.height % h.max_size == 0;
+    const uint32_t mcols = h.width / h.min_size, mrows = h.height / h.min_size;
+    // layout pass: reads only the stream buffer (the body and kFrc1PadWords zeroed dwords after it)
+    uint32_t status[2] = {0, 0};
+    if (n) {
+        const size_t body_words = (size_t)(h.body_bytes / 4); // every section is whole dwords
+        uint32_t max_nodes = 1, max_bm_words = 1;
+        for (uint32_t k = 0; k < h.levels; ++k) {
+            if (k)
+                max_nodes = std::max(max_nodes, h.nodes[k]);
+            if (k + 1 < h.levels)
+                max_bm_words = std::max(max_bm_words, (h.nodes[k] + 31) / 32);
+        }
+        FRAC_HIP(c, c->d_frq_in.ensure(body_words + kFrc1PadWords));
+        FRAC_HIP(c, c->d_frq_nodes[0].ensure(max_nodes));
+        FRAC_HIP(c, c->d_frq_nodes[1].ensure(max_nodes));
+        FRAC_HIP(c, c->d_frq_rank.ensure(max_bm_words));
+        FRAC_HIP(c, c->d_frq_leaves.ensure(n));
+        FRAC_HIP(c, c->d_frc_status.ensure(2));
+        if (tiles)
+            FRAC_HIP(c, c->d_frq_map.ensure((size_t)mcols * mrows));
+        using PopcIter = hipcub::TransformInputIterator<uint32_t, Frq1Popc, const uint32_t*>;
+        size_t need = 0;
+        FRAC_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, need, PopcIter(c->d_frq_in.ptr, Frq1Popc()),
+                                                     c->d_frq_rank.ptr, (int)max_bm_words, c->stream));
+        if (need > c->qt_tmp_bytes) {
+            FRAC_HIP(c, c->d_qt_tmp.ensure(need));
+            c->qt_tmp_bytes = need;
+        }
+        FRAC_HIP(c, hipMemsetAsync(c->d_frq_in.ptr + body_words, 0, kFrc1PadWords * sizeof(uint32_t), c->stream));
+        FRAC_HIP(c, hipMemsetAsync(c->d_frc_status.ptr, 0, sizeof(status), c->stream));
+        FRAC_HIP(c, hipMemcpyAsync(c->d_frq_in.ptr, stream + FRAC_FRQ1_HEADER_BYTES, (size_t)h.body_bytes,
+                                   hipMemcpyHostToDevice, c->stream));
+        uint32_t leaf_base = 0;
+        for (uint32_t k = 0; k < h.levels; ++k) {
+            const uint32_t N = h.nodes[k];
+            if (!N)
+                break; // no node, none below
+            Frq1Level lv{};
+            lv.n_nodes = N;
+            lv.lg = frq1_bitlen(h.max_size >> k) - 1;
+            lv.cols0 = k ? 0 : h.width / h.max_size;
+            lv.has_bitmap = k + 1 < h.levels;
+            lv.bitmap_word = (uint32_t)((h.bitmap_offset[k] - FRAC_FRQ1_HEADER_BYTES) / 4);
+            lv.rec_word = (uint32_t)((h.record_offset[k] - FRAC_FRQ1_HEADER_BYTES) / 4);
+            lv.leaf_base = leaf_base;
+            lv.n_domains = h.n_domains[k];
+            lv.index_bits = h.index_bits[k];
+            lv.c_bits = h.contrast_bits;
+            lv.b_bits = h.brightness_bits;
+            lv.t_bits = h.record_bits[k] - h.index_bits[k] - h.contrast_bits - h.brightness_bits;
+            lv.record_bits = h.record_bits[k];
+            lv.mcols = tiles ? mcols : 0;
+            lv.cell_lg = frq1_bitlen(h.min_size) - 1;
+            if (lv.has_bitmap) {
+                size_t tb = c->qt_tmp_bytes;
+                FRAC_HIP(c, hipcub::DeviceScan::ExclusiveSum(c->d_qt_tmp.ptr, tb,
+                                                             PopcIter(c->d_frq_in.ptr + lv.bitmap_word, Frq1Popc()),
+                                                             c->d_frq_rank.ptr, (int)((N + 31) / 32), c->stream));
+            }
+            frq1dec_level<<<(N + 255) / 256, 256, 0, c->stream>>>(c->d_frq_in.ptr, lv, c->d_frq_rank.ptr,
+                                                                 c->d_frq_nodes[k & 1].ptr, c->d_frq_nodes[(k + 1) & 1].ptr,
+                                                                 c->d_frq_leaves.ptr, c->d_frq_map.ptr,
+                                                                 c->d_frc_status.ptr);
+            leaf_base += h.leaves[k];
+        }
+        FRAC_HIP(c, hipGetLastError());
+        FRAC_HIP(c, hipMemcpyAsync(status, c->d_frc_status.ptr, sizeof(status), hipMemcpyDeviceToHost, c->stream));
+        FRAC_HIP(c, hipStreamSynchronize(c->stream));
+        if (status[0])
+            return c->fail(FRAC_E_INVALID, "FRQ1: domain index out of range");
+    }
+    const bool whole = tiles && status[1] == 0; // every pixel written by a leaf with a domain
+    if (whole && !(c->p.flags & FRAC_FLAG_DECODE_STEPWISE)) {
+        Frq1StepArgs a;
+        a.w = W;
+        a.h = H;
+        a.scale = scale;
+        a.cell = h.min_size * scale;
+        a.mcols = mcols;
+        a.map = c->d_frq_map.ptr;
+        a.leaves = c->d_frq_leaves.ptr;
+        const dim3 grid((W + kFrc1TileW - 1) / kFrc1TileW, (H + kFrc1TileH - 1) / kFrc1TileH);
+        return decode_fused_loop(c, W, H, max_iter < 0 ? 300 : max_iter, rms_eps, plane, iterations, rms,
+                                 [&](const uint8_t* src, uint8_t* tgt, uint32_t stride) {
+                                     a.src = src;
+                                     a.tgt = tgt;
+                                     a.stride = stride;
+                                     frq1dec_step<<<grid, 256, 0, c->stream>>>(a, L, c->d_dec_state.ptr,
+                                                                               c->d_dec_part.ptr);
+                                 });
+    }
+    // every other stream: the leaves as scaled encode items, through the item decoder (fused when they
+    // tile the plane and every leaf has a domain, as frac_decode decides)
+    FRAC_HIP(c, c->d_dec_items.ensure(n));
+    if (n) {
+        frq1dec_expand<<<(n + 255) / 256, 256, 0, c->stream>>>(c->d_frq_leaves.ptr, L, scale, c->d_dec_items.ptr);
+        FRAC_HIP(c, hipGetLastError());
+    }
+    return decode_impl(c, c->d_dec_items.ptr, n, W, H, max_iter, rms_eps, plane, iterations, rms, whole);
+}
+
 } // extern "C"

@@ -258,6 +258,10 @@ struct frac_ctx {
     DBuf<unsigned long long> d_frc_rec;
     DBuf<uint32_t> d_frc_words;
     DBuf<uint32_t> d_frc_in, d_frc_status; // frac_decode_frc1: the padded stream body; {bad, domain-less} counts
+    // frac_decode_frq1: the padded body; the levels' node origins (two buffers, level k reads one and writes the
+    // other); a level's per-dword split ranks; the leaf entries; the fast path's leaf number per min_size cell
+    DBuf<uint32_t> d_frq_in, d_frq_nodes[2], d_frq_rank, d_frq_map;
+    DBuf<uint4> d_frq_leaves;
     // quadtree: the per-level domain grids (geometry only) of the last frame size, by log2(n)
     uint32_t qt_w = 0, qt_h = 0;
     std::vector<frac_grid_item> qt_doms[5];

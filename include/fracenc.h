@@ -161,7 +161,7 @@ const char* frac_last_error(const frac_ctx* ctx);
  * frac_decode_results — returns FRAC_E_STATE, and frac_device_results returns NULL: the old winners are never
  * paired with the new parameters, domain list, ranges or planes.  A setter that fails its own argument checks
  * changes nothing.  frac_set_stream, frac_set_tuple_sink, frac_sync, frac_classify_items, frac_decode,
- * frac_decode_frc1 and the colour conversion leave the results readable. */
+ * frac_decode_frc1, frac_decode_frq1 and the colour conversion leave the results readable. */
 int frac_set_params(frac_ctx* ctx, const frac_params* params);
 
 /* Planes are uint8, row-major with the given stride (bytes). Copied to the device.
@@ -359,6 +359,60 @@ int frac_frc1_info(const uint8_t* stream, size_t len, struct frac_frc1_info* out
  * is its capacity.  A record whose index equals n_domains has no domain and its range is left
  * untouched; an index above n_domains fails the call (FRAC_E_INVALID) before any plane is touched. */
 int frac_decode_frc1(frac_ctx* ctx, const uint8_t* stream, size_t len, uint32_t scale, int max_iter,
+                     double rms_eps, uint8_t* plane, size_t plane_bytes, int* iterations, double* rms);
+
+/* ---- FRQ1: the quadtree's leaves as a stream, packed on the host, decoded on the device ----
+ * These three symbols were added after ABI 9 without changing FRAC_ABI_VERSION: probe for them by
+ * name (dlsym) when the library may be older.
+ *
+ * FRQ1 (fractencode_amd/codec.py documents the layout) holds, after a 64-byte header, per level of the
+ * quadtree a split bitmap over the level's nodes (all but the last level) and the level's leaves as
+ * (domain index, transform, q_contrast, q_brightness) records, bit-packed as FRC1's, in the order
+ * frac_encode_quadtree emits them.  One quantizer pair covers the stream.
+ *
+ * The header's fields plus what a walk over the bitmaps derives; levels k = 0 .. levels − 1 have the sides
+ * max_size >> k, entries past `levels` are 0.  Offsets are bytes from the start of the stream. */
+#define FRAC_FRQ1_HEADER_BYTES 64
+struct frac_frq1_info {
+    uint32_t width, height, max_size, min_size;
+    uint32_t transforms, contrast_bits, brightness_bits, flags;
+    uint32_t n_leaves, levels;
+    uint32_t nodes[4], leaves[4];     /* N_k, M_k = N_k − (split nodes) */
+    uint32_t n_domains[4];            /* frac_uniform_grid(2·n_k, n_k) counts */
+    uint32_t index_bits[4], record_bits[4];
+    uint64_t bitmap_offset[4], record_offset[4];
+    uint64_t body_bytes;
+    double contrast_min, contrast_max, brightness_min, brightness_max;
+};
+/* Host only, no device and no ctx: parse an FRQ1 stream, walk its split bitmaps (popcounts) to find every
+ * section, and validate it against the stream length (message via frac_last_error(NULL)).  FRAC_E_INVALID
+ * for: len < 64; wrong magic or version; a zero width or height, or a side above 65535; max_size or
+ * min_size outside {2, 4, 8, 16}, min_size > max_size; transforms outside 1..8; contrast_bits or
+ * brightness_bits outside [2, 24]; a non-zero reserved byte or word; a level's record wider than 64 bits;
+ * a stream that ends inside a bitmap or record section; a set padding bit in a bitmap; n_leaves other than
+ * the levels' leaf count; a non-finite min or max.  Trailing bytes are ignored. */
+int frac_frq1_info(const uint8_t* stream, size_t len, struct frac_frq1_info* out);
+/* Host only, no ctx: n leaves of frac_encode_quadtree_leaves (its output order) of a width×height frame
+ * encoded with (max_size, min_size) as an FRQ1 stream.  The leaves are on the host already and the pack is
+ * one pass over them, so it runs there, in FP64 (Quantizer::quantized, encode/Quantizer.hpp:7-45).
+ * stream_flags goes into the header's flags (bit 0: the classifier was on).  *n_out = stream size; writes
+ * min(cap, size) bytes (out may be NULL to query the size).  FRAC_E_INVALID (message via
+ * frac_last_error(NULL)) for: contrast_bits or brightness_bits outside [2, 16]; sizes or sides as
+ * frac_frq1_info refuses them; transforms outside 1..8; a leaf that is not the next leaf of the canonical
+ * order (a size code outside the levels, a position that is no node of its level, a leaf out of order,
+ * missing or surplus); a domain index that is neither below its level's domain count nor
+ * FRAC_QT_NO_DOMAIN; a transform >= transforms; a non-finite contrast or brightness. */
+int frac_pack_frq1(const frac_qt_leaf* leaves, size_t n, uint32_t width, uint32_t height, uint32_t max_size,
+                   uint32_t min_size, uint32_t transforms, uint32_t stream_flags, uint32_t contrast_bits,
+                   uint32_t brightness_bits, uint8_t* out, size_t cap, size_t* n_out);
+/* Decoder2::decode of the stream's leaves with every coordinate and size multiplied by `scale`: the result
+ * of frac_decode on the stream's dequantized records so scaled.  scale, plane, plane_bytes, max_iter,
+ * rms_eps, iterations and rms exactly as frac_decode_frc1's.  A leaf whose index equals its level's domain
+ * count has no domain and its range is left untouched; an index above it fails the call (FRAC_E_INVALID)
+ * before any plane is touched.  The layout (ranks of the split bits by a prefix sum, leaf origins, the
+ * records' bit windows) is computed on the device; only the body is uploaded.  Streams with a level of
+ * 2^24 or more domains are refused (as frac_qt_leaf cannot name them). */
+int frac_decode_frq1(frac_ctx* ctx, const uint8_t* stream, size_t len, uint32_t scale, int max_iter,
                      double rms_eps, uint8_t* plane, size_t plane_bytes, int* iterations, double* rms);
 
 /* ---- host helpers (no device needed) ------------------------------------ */

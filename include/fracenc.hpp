@@ -12,7 +12,8 @@
 //                       thread-dependent, :165-168)
 //   Quantizer<T>        Frac::Quantizer (encode/Quantizer.hpp:7-45) as the built reference
 //                       computes it (value() with the FMA the compiler contracts)
-//   createUniformGrid / preclassify / encodeQuadtree / decode / decode_frc1 / frc1_info — the C ABI entry points
+//   createUniformGrid / preclassify / encodeQuadtree / decode / decode_frc1 / frc1_info / decode_frq1 / frq1_info /
+//                       pack_frq1 — the C ABI entry points
 //   Engine's ABI 8/9 methods: an external HIP stream (void*), the tuple sink and 32-byte tuples,
 //                       frame streaming (setFrameAsync / setFrameDeviceAsync), 32-byte quadtree
 //                       leaves, per-run device times
@@ -87,6 +88,33 @@ inline Frc1Info frc1_info(const uint8_t* stream, size_t len)
     if (frac_frc1_info(stream, len, &info) != FRAC_OK)
         throw Error(std::string("fracenc: ") + frac_last_error(nullptr));
     return info;
+}
+
+// The same for an FRQ1 quadtree stream: header, per-level counts and section offsets (frac_frq1_info).
+using Frq1Info = struct ::frac_frq1_info;
+inline Frq1Info frq1_info(const uint8_t* stream, size_t len)
+{
+    Frq1Info info{};
+    if (frac_frq1_info(stream, len, &info) != FRAC_OK)
+        throw Error(std::string("fracenc: ") + frac_last_error(nullptr));
+    return info;
+}
+
+// Quadtree leaves (Engine::encodeQuadtreeLeaves' order) as an FRQ1 stream, packed on the host (frac_pack_frq1).
+inline std::vector<uint8_t> pack_frq1(const std::vector<frac_qt_leaf>& leaves, uint32_t w, uint32_t h,
+                                      uint32_t max_size, uint32_t min_size, uint32_t transforms = 4,
+                                      bool use_classifier = false, uint32_t contrast_bits = 5,
+                                      uint32_t brightness_bits = 7)
+{
+    size_t n = 0;
+    std::vector<uint8_t> out;
+    for (int pass = 0; pass < 2; ++pass) {
+        if (frac_pack_frq1(leaves.data(), leaves.size(), w, h, max_size, min_size, transforms, use_classifier ? 1u : 0u,
+                           contrast_bits, brightness_bits, pass ? out.data() : nullptr, out.size(), &n) != FRAC_OK)
+            throw Error(std::string("fracenc: ") + frac_last_error(nullptr));
+        out.resize(n);
+    }
+    return out;
 }
 
 class Engine {
@@ -226,6 +254,25 @@ public:
                                        uint32_t scale = 1, int max_iter = -1, double rms_eps = 1e-5)
     {
         return decode_frc1(stream.data(), stream.size(), plane, scale, max_iter, rms_eps);
+    }
+    // The same for an FRQ1 quadtree stream (frac_decode_frq1).
+    std::pair<int, double> decode_frq1(const uint8_t* stream, size_t len, std::vector<uint8_t>& plane,
+                                       uint32_t scale = 1, int max_iter = -1, double rms_eps = 1e-5)
+    {
+        const Frq1Info info = frq1_info(stream, len);
+        const uint32_t k = scale >= 1 && scale <= 16 ? scale : 0; // the library refuses the scale itself
+        const size_t need = (size_t)k * info.width * k * info.height;
+        if (plane.size() != need)
+            plane.assign(need, 0);
+        int it = 0;
+        double rms = 0.0;
+        check(frac_decode_frq1(ctx_, stream, len, scale, max_iter, rms_eps, plane.data(), plane.size(), &it, &rms));
+        return {it, rms};
+    }
+    std::pair<int, double> decode_frq1(const std::vector<uint8_t>& stream, std::vector<uint8_t>& plane,
+                                       uint32_t scale = 1, int max_iter = -1, double rms_eps = 1e-5)
+    {
+        return decode_frq1(stream.data(), stream.size(), plane, scale, max_iter, rms_eps);
     }
 
 private:
