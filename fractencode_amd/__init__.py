@@ -235,6 +235,8 @@ def lib() -> C.CDLL:
             "frac_classify": (i32, [vp, u32, u32, u32, vp, sz]),
             "frac_transform_index": (i32, [u32, u32, u32]),
             "frac_hit_limit": (C.c_int64, [C.c_double, u32]),
+            "frac_debug_sort_chunk": (u32, []),
+            "frac_debug_sort_pairs": (i32, [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp, vp]),
         }
         for name, (res, args) in sig.items():
             if os.environ.get("FRAC_LIB") and not hasattr(L, name):
@@ -261,6 +263,30 @@ def build_info() -> dict:
 def last_error(ctx=None) -> str:
     msg = lib().frac_last_error(ctx)
     return msg.decode() if msg else ""
+
+
+# ---- test hooks (outside the ABI contract) ------------------------------------------
+
+TP_SORT_CHUNK = 2048  # items per workgroup of the tiled SEA form's sort (frac_debug_sort_chunk)
+
+
+def debug_sort_pairs(keys, vals, keys_b, vals_b, bits: int):
+    """Test hook: the tiled SEA form's stable sort of (key, value) uint32 pairs on the current device, two
+    sides through the same launches (either may be empty), on the low `bits` key bits.  Returns
+    (keys, vals, keys_b, vals_b) sorted, equal keys in input order."""
+    L = lib()
+    if L.frac_debug_sort_chunk() != TP_SORT_CHUNK:
+        raise FracError("TP_SORT_CHUNK differs from the library's frac_debug_sort_chunk()")
+    ins = [np.ascontiguousarray(a, dtype=np.uint32) for a in (keys, vals, keys_b, vals_b)]
+    if ins[0].shape != ins[1].shape or ins[2].shape != ins[3].shape or ins[0].ndim != 1 or ins[2].ndim != 1:
+        raise ValueError("keys and values must be one-dimensional and of equal length per side")
+    outs = [np.empty_like(a) for a in ins]
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
+    rc = L.frac_debug_sort_pairs(ptr(ins[0]), ptr(ins[1]), ins[0].size, ptr(ins[2]), ptr(ins[3]), ins[2].size,
+                                 bits, *[ptr(a) for a in outs])
+    if rc != 0:
+        raise FracError(f"frac_debug_sort_pairs: {last_error()} (code {rc})")
+    return tuple(outs)
 
 
 # ---- host helpers ----------------------------------------------------------------

@@ -35,6 +35,7 @@
 #include "fracenc_frc1dec.hip"
 #include "fracenc_frq1dec.hip"
 #include "fracenc_tp.hip"
+#include "fracenc_tpsort.hip"
 #include "fracenc_gen.hip"
 #include "fracenc_bucket.hip"
 
@@ -165,6 +166,45 @@ const char* frac_build_id(void) { return FRAC_SOURCE_ID; }
 int frac_build_flags(void) { return kTuningBuild ? FRAC_BUILD_TUNING : 0; }
 
 const char* frac_last_error(const frac_ctx* ctx) { return ctx ? ctx->err.c_str() : g_last_error.c_str(); }
+
+uint32_t frac_debug_sort_chunk(void) { return kTpSortChunk; }
+
+// Test hook: the tiled form's sort (tp_sort_pairs) on host arrays, both sides through the same launches on the
+// current device's null stream, then a synchronous copy back.
+int frac_debug_sort_pairs(const uint32_t* keys, const uint32_t* vals, uint32_t n, const uint32_t* keys_b,
+                          const uint32_t* vals_b, uint32_t n_b, uint32_t bits, uint32_t* out_keys, uint32_t* out_vals,
+                          uint32_t* out_keys_b, uint32_t* out_vals_b)
+{
+    auto bad = [](const std::string& m, int code) {
+        g_last_error = m;
+        return code;
+    };
+    if (bits == 0 || bits > 32)
+        return bad("frac_debug_sort_pairs: bits must be 1..32", FRAC_E_INVALID);
+    if ((n && !(keys && vals && out_keys && out_vals)) || (n_b && !(keys_b && vals_b && out_keys_b && out_vals_b)))
+        return bad("frac_debug_sort_pairs: NULL array", FRAC_E_INVALID);
+    DBuf<uint32_t> d[2][4], table; // per side: key, val, key2, val2
+    const uint32_t* in[2][2] = {{keys, vals}, {keys_b, vals_b}};
+    uint32_t* out[2][2] = {{out_keys, out_vals}, {out_keys_b, out_vals_b}};
+    const uint32_t cnt[2] = {n, n_b};
+    hipError_t e = table.ensure(tp_sort_table_words(n, n_b));
+    for (int s = 0; s < 2 && e == hipSuccess; ++s) {
+        for (int k = 0; k < 4 && e == hipSuccess; ++k)
+            e = d[s][k].ensure(cnt[s]);
+        for (int k = 0; k < 2 && e == hipSuccess && cnt[s]; ++k)
+            e = hipMemcpy(d[s][k].ptr, in[s][k], (size_t)cnt[s] * sizeof(uint32_t), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess)
+        e = tp_sort_pairs(table.ptr, TpSortBufs{d[0][0].ptr, d[0][1].ptr, d[0][2].ptr, d[0][3].ptr, n},
+                          TpSortBufs{d[1][0].ptr, d[1][1].ptr, d[1][2].ptr, d[1][3].ptr, n_b}, bits, nullptr);
+    const int from = tp_sort_in_second(bits) ? 2 : 0;
+    for (int s = 0; s < 2 && e == hipSuccess; ++s)
+        for (int k = 0; k < 2 && e == hipSuccess && cnt[s]; ++k)
+            e = hipMemcpy(out[s][k], d[s][from + k].ptr, (size_t)cnt[s] * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess)
+        return bad(std::string("frac_debug_sort_pairs: ") + hipGetErrorString(e), FRAC_E_DEVICE);
+    return FRAC_OK;
+}
 
 frac_ctx* frac_create(int device, const frac_params* params)
 {

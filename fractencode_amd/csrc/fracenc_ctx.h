@@ -108,10 +108,6 @@ struct frac_ctx {
     // the streams come before every buffer: members go in reverse order, the buffers first
     Stream own_stream;
     hipStream_t stream = nullptr; // own_stream, or the caller's (frac_set_stream)
-    // the tiled form's range sort runs here, beside the domain sort on `stream` (launch_tp: forked after tp_keys,
-    // joined before tp_build in the same call, so nothing of a run is left on it when launch_tp returns its
-    // stream to the caller); created on the first tiled run
-    Stream tp_aux_stream;
     // frac_set_frame_async (ABI 9): the frame after the current one is uploaded into d_src_next on copy_stream
     // while the context's stream still reads d_src; the two swap at the call (created on first use).
     // Frame streaming from host memory: the upload runs on the context's copy stream into the plane buffer the
@@ -252,8 +248,7 @@ struct frac_ctx {
     uint64_t tp_full_pairs = 0; // block × tile pairs with every window open (Σ groups: blocks · bucket tiles)
     uint64_t tp_seed_pairs = 0; // block × tile pairs of the seed search (Σ groups: blocks)
     DBuf<int32_t> d_tp_rbk;
-    DBuf<uint8_t> d_tp_sort_tmp; // the range sort's own scratch (sea_tmp_bytes): the two sorts run at the same time
-    Event tp_fork, tp_join;
+    DBuf<uint32_t> d_tp_sort_table; // tp_sort_pairs' digit tables, both sides (fill_tp: tp_sort_table_words)
     DBuf<Frc1MinMax> d_frc_mm;             // frac_pack_frc1
     DBuf<unsigned long long> d_frc_rec;
     DBuf<uint32_t> d_frc_words;
@@ -314,8 +309,6 @@ struct frac_ctx {
             (void)hipStreamSynchronize(stream);
         if (frame.copy_stream)
             (void)hipStreamSynchronize(frame.copy_stream);
-        if (tp_aux_stream)
-            (void)hipStreamSynchronize(tp_aux_stream);
     }
 
     int fail(int code, const std::string& msg)

@@ -687,9 +687,11 @@ int launch_mfma(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool inits =
 // SEA engine, tiled form (fracenc_tp.hip): sorted tiles and blocks, per-range seed bounds,
 // per-group windows, the Fourier search over the windows with one record per block and lane, resolve_dft.
 // No buffer is sized from the windows (the records are nblocks·64, allocated at prepare()); one host
-// synchronisation remains, for the run's totals: frac_stats' counts and the budget test.
-// Outside the two sorts the route is nine commands: tp_keys (with the run's resets), tp_build, tp_prep, the seed
-// search_dft, tp_seed_windows, tp_plan (the totals), the synchronisation, search_dft and resolve_dft.
+// synchronisation remains, for the run's totals: frac_stats' counts and the budget test.  (The windowed search
+// queued before it, skipped on the device when over the budget, measured no gain: DESIGN §7.9.)
+// The route is tp_keys (with the run's resets), the sort's three launches per key byte (tp_sort_count,
+// tp_sort_offsets, tp_sort_scatter: six at 16-bit keys, nine with buckets), tp_build, tp_prep, the seed search_dft,
+// tp_seed_windows, tp_plan (the totals), the synchronisation, search_dft and resolve_dft, all on one stream.
 // budgeted (FRAC_ENGINE_AUTO's pruned route): when the windows hold more than kAutoPruneBudget of the run's
 // block × tile pairs the attempt is abandoned before the windowed search is launched, and the exhaustive
 // Fourier search (launch_dft) produces the records in the same run on the same stream.
@@ -728,48 +730,20 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
         k.fb_count = c->d_fb_count.ptr;
         tp_keys<<<k.dblocks + (nr + 255) / 256, 256, 0, c->stream>>>(k);
     }
-    // The two sorts do not depend on each other, and a pass over so few items is bound by its look-back chain,
-    // not by bandwidth: the range sort goes to the context's auxiliary stream, with scratch of its own, forked
-    // after tp_keys (so after everything this stream waited for: an upload, the previous run) and joined before
-    // tp_build.  Nothing returns between the fork and the join's wait, whatever failed in between.
-    hipError_t rsort = hipSuccess, dsort = hipSuccess, join = hipSuccess;
-    if (nr && P) {
-        if (!c->tp_aux_stream) {
-            FRAC_HIP(c, hipStreamCreateWithFlags(&c->tp_aux_stream.s, hipStreamNonBlocking));
-            FRAC_HIP(c, hipEventCreateWithFlags(&c->tp_fork.e, hipEventDisableTiming));
-            FRAC_HIP(c, hipEventCreateWithFlags(&c->tp_join.e, hipEventDisableTiming));
-        }
-        FRAC_HIP(c, hipEventRecord(c->tp_fork, c->stream));
-        FRAC_HIP(c, hipStreamWaitEvent(c->tp_aux_stream, c->tp_fork, 0));
-        size_t tb = c->sea_tmp_bytes;
-        rsort = sort_pairs_u32(c->d_tp_sort_tmp.ptr, tb, c->d_sea_rkey.ptr, c->d_sea_rkey2.ptr, c->d_sea_rord.ptr,
-                               c->d_sea_rord2.ptr, nr, c->tp_key_bits, c->tp_aux_stream);
-        join = hipEventRecord(c->tp_join, c->tp_aux_stream);
-    } else if (nr) {
-        size_t tb = c->sea_tmp_bytes;
-        rsort = sort_pairs_u32(c->d_sea_tmp.ptr, tb, c->d_sea_rkey.ptr, c->d_sea_rkey2.ptr, c->d_sea_rord.ptr,
-                               c->d_sea_rord2.ptr, nr, c->tp_key_bits, c->stream);
-    }
-    if (P) {
-        size_t tb = c->sea_tmp_bytes;
-        dsort = sort_pairs_u32(c->d_sea_tmp.ptr, tb, c->d_sea_dkey.ptr, c->d_sea_dkey2.ptr, c->d_sea_dpos.ptr,
-                               c->d_sea_dpos2.ptr, P, c->tp_key_bits, c->stream);
-    }
-    if (nr && P) {
-        if (join == hipSuccess)
-            join = hipStreamWaitEvent(c->stream, c->tp_join, 0);
-        if (join != hipSuccess) // no event, or no wait on it: the host waits for the auxiliary stream itself
-            (void)hipStreamSynchronize(c->tp_aux_stream);
-    }
-    FRAC_HIP(c, rsort);
-    FRAC_HIP(c, dsort);
-    FRAC_HIP(c, join);
+    // Both sides' sorts in the same launches (fracenc_tpsort.hip): stable, tp_key_bits / 8 passes of three small
+    // kernels each on this stream, into the tables fill_tp sized.  An even number of passes leaves the sorted
+    // pairs in the buffers tp_keys wrote, an odd one in their twins.
+    FRAC_HIP(c, tp_sort_pairs(c->d_tp_sort_table.ptr,
+                              TpSortBufs{c->d_sea_dkey.ptr, c->d_sea_dpos.ptr, c->d_sea_dkey2.ptr, c->d_sea_dpos2.ptr, P},
+                              TpSortBufs{c->d_sea_rkey.ptr, c->d_sea_rord.ptr, c->d_sea_rkey2.ptr, c->d_sea_rord2.ptr, nr},
+                              c->tp_key_bits, c->stream));
+    const bool twin = tp_sort_in_second(c->tp_key_bits);
     // the tiles and the slots from the two sorted orders
     if (nt || nbk) {
         TpBuildArgs t;
         t.bk = c->tp_bk;
-        t.skey = c->d_sea_dkey2.ptr;
-        t.spos = c->d_sea_dpos2.ptr;
+        t.skey = twin ? c->d_sea_dkey2.ptr : c->d_sea_dkey.ptr;
+        t.spos = twin ? c->d_sea_dpos2.ptr : c->d_sea_dpos.ptr;
         t.ntiles = nt;
         t.tile_pos = c->d_tp_tile_pos.ptr;
         t.tile_sd = c->d_tp_tile_sd.ptr;
@@ -779,8 +753,8 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
         t.tguard = c->d_dft_tguard.ptr;
         t.ks = kTpKS;
         t.tblocks = (nt * 32 + 255) / 256;
-        t.rkey = c->d_sea_rkey2.ptr;
-        t.rord = c->d_sea_rord2.ptr;
+        t.rkey = twin ? c->d_sea_rkey2.ptr : c->d_sea_rkey.ptr;
+        t.rord = twin ? c->d_sea_rord2.ptr : c->d_sea_rord.ptr;
         t.nblocks = nbk;
         t.slot_range = c->d_tp_slot_range.ptr;
         t.range_slot = c->d_tp_range_slot.ptr;

@@ -114,7 +114,7 @@ constexpr int kTpVar = 1 | kDftChain | (kDftTpForm == 6 ? kDft6 : 0); // the SEA
 constexpr uint32_t kTpKS = kDftTpForm == 4 ? 4u : 5u;                    // its domain fragments per tile
 // FRAC_ENGINE_AUTO's pruned route (n = 8, T = 4, ratio 2; DESIGN §4.4, measured in §7.4).
 // kAutoPruneMinPairs: the fewest block × tile pairs (every window open) at which AUTO tries the bound; below
-// it the route's fixed cost — two radix sorts, about ten small launches, one host turnaround — is too large a
+// it the route's fixed cost — the two sides' sort, about ten small launches, one host turnaround — is too large a
 // share of the run to risk on unknown data (FRAC_FLAG_PRUNE ignores it).
 // kAutoPruneBudget: the share of those pairs the windows may hold; above it the windowed search with its exact
 // epilogue and its resolve costs what the exhaustive search does, and the run falls back to that.  (It bounds
@@ -773,7 +773,7 @@ int fill_tp(frac_ctx* c, const PrepBuckets& B)
     FRAC_HIP(c, c->d_tp_blk_sr.ensure(nbk));
     FRAC_HIP(c, c->d_tp_blk_u.ensure(nbk));
     FRAC_HIP(c, c->h_tp_tot.ensure());
-    FRAC_HIP(c, c->d_tp_sort_tmp.ensure(c->sea_tmp_bytes)); // (fill_sea ran: the larger of the sorts' needs)
+    FRAC_HIP(c, c->d_tp_sort_table.ensure(tp_sort_table_words(P, nr)));
     FRAC_HIP(c, c->d_tp_pairs.ensure(ng));
     FRAC_HIP(c, c->d_tp_evals.ensure(ng));
     FRAC_HIP(c, c->d_tp_rbk.ensure(nr));

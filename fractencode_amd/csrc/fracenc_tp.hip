@@ -20,8 +20,10 @@
 //     more attain the maximum than are listed: ties still go to the earliest domain, then the
 //     later transform.  The seed search is the same kernel over a one-tile window and writes
 //     the same records, which tp_seed_windows reads before the windowed search replaces them.
+// Both sides are sorted by fracenc_tpsort.hip, in the same launches on the run's stream.
 // Nothing is sized from the windows; the host still waits once per run, for the totals
-// (frac_stats, and AUTO's budget test), which tp_plan sums into its pinned block.
+// (frac_stats, and AUTO's budget test), which tp_plan sums into its pinned block.  (Queueing the windowed
+// search before that wait, behind a device-side budget test, measured no gain: DESIGN §7.9.)
 // Records are identical to the exhaustive search's; the cost is data-dependent.
 #include "fracenc_common.h"
 
