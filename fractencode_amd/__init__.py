@@ -119,6 +119,15 @@ class FracFrq1Info(C.Structure):
                [(k, C.c_double) for k in ("contrast_min", "contrast_max", "brightness_min", "brightness_max")]
 
 
+class FracFrc3Info(C.Structure):
+    """struct frac_frc3_info: an FRC3 container's header, plus each plane stream's kind and place."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("kind", C.c_uint32 * 3),
+                ("offset", C.c_uint64 * 3), ("length", C.c_uint64 * 3), ("total_bytes", C.c_uint64)]
+
+
+KIND_FRC1, KIND_FRQ1 = 1, 2  # frac_frc3_info.kind
+
+
 class FracError(RuntimeError):
     pass
 
@@ -230,6 +239,14 @@ def lib() -> C.CDLL:
                                                   C.POINTER(FracStats)]),
             "frac_rgb_to_yuv_device": (i32, [vp, vp, u32, u32, u32, vp, u32, vp, u32, vp, u32]),
             "frac_rgb_to_yuv": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]),
+            "frac_yuv_to_rgb_device": (i32, [vp, vp, u32, u32, u32, vp, u32, vp, u32, vp, u32]),
+            "frac_yuv_to_rgb": (i32, [vp, vp, vp, vp, u32, u32, vp, u32]),
+            "frac_frc3_info": (i32, [vp, sz, C.POINTER(FracFrc3Info)]),
+            "frac_pack_frc3": (i32, [C.POINTER(vp), C.POINTER(sz), u32, u32, vp, sz, C.POINTER(C.c_size_t)]),
+            "frac_decode_frc3": (i32, [vp, vp, sz, u32, i32, C.c_double, vp, u32, sz, C.POINTER(C.c_int),
+                                       C.POINTER(C.c_double)]),
+            "frac_decode_frc3_device": (i32, [vp, vp, sz, u32, i32, C.c_double, vp, u32, sz, C.POINTER(C.c_int),
+                                              C.POINTER(C.c_double)]),
             "frac_uniform_grid": (sz, [u32, u32, u32, u32, vp, sz]),
             "frac_uniform_grid2": (sz, [u32, u32, u32, u32, u32, u32, vp, sz]),
             "frac_classify": (i32, [vp, u32, u32, u32, vp, sz]),
@@ -351,6 +368,45 @@ def pack_frq1(leaves: np.ndarray, width: int, height: int, max_size: int, min_si
     if lib().frac_pack_frq1(*args, buf.ctypes.data_as(C.c_void_p), n.value, C.byref(n)) != 0:
         raise FracError(last_error())
     return buf.tobytes()
+
+
+def frc3_info(stream) -> dict:
+    """An FRC3 colour container's header and plane streams, validated on the host (frac_frc3_info): width,
+    height, flags, per plane kind (KIND_FRC1 / KIND_FRQ1), offset and length, and total_bytes — the keys of
+    codec.unpack_color_stream's header dict.  Raises FracError on a container frac_decode_frc3 would refuse by
+    its header or by a plane stream's."""
+    buf = np.frombuffer(stream, dtype=np.uint8)
+    out = FracFrc3Info()
+    if lib().frac_frc3_info(buf.ctypes.data if len(buf) else None, len(buf), C.byref(out)) != 0:
+        raise FracError(last_error())
+    return {k: (list(getattr(out, k)) if hasattr(getattr(out, k), "__len__") else getattr(out, k))
+            for k, _ in FracFrc3Info._fields_}
+
+
+def pack_frc3(streams, width: int, height: int) -> bytes:
+    """The Y, U and V plane streams (FRC1 or FRQ1, kinds may be mixed) of a width × height RGB frame as one FRC3
+    container (codec.py layout; frac_pack_frc3)."""
+    if len(streams) != 3:
+        raise FracError("pack_frc3: three plane streams (Y, U, V)")
+    bufs = [np.frombuffer(s, dtype=np.uint8) for s in streams]
+    ptrs = (C.c_void_p * 3)(*[b.ctypes.data if len(b) else None for b in bufs])
+    lens = (C.c_size_t * 3)(*[len(b) for b in bufs])
+    n = C.c_size_t(0)
+    if lib().frac_pack_frc3(ptrs, lens, width, height, None, 0, C.byref(n)) != 0:
+        raise FracError(last_error())
+    out = np.empty(n.value, dtype=np.uint8)
+    if lib().frac_pack_frc3(ptrs, lens, width, height, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)) != 0:
+        raise FracError(last_error())
+    return out.tobytes()
+
+
+def _device_rows(t, width_bytes: int, what: str) -> int:
+    """The row stride in bytes of a CUDA uint8 tensor whose rows hold width_bytes contiguous bytes; FracError for
+    a negative or too small one (ctypes would wrap it into a huge uint32)."""
+    stride = int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), width_bytes)
+    if stride < width_bytes or stride > 0xFFFFFFFF:
+        raise FracError(f"{what}: row stride {t.stride(0)} is negative or below the row's {width_bytes} bytes")
+    return stride
 
 
 def transform_index(n: int, t: int, pix: int) -> int:
@@ -694,6 +750,69 @@ class Engine:
                                           v.ctypes.data))
         return y, u, v
 
+    def yuv_to_rgb(self, y, u, v):
+        """ImageIO::yuv2rgb on the device (image/ImageIO.cpp:68-84), the inverse of rgb_to_yuv's layout.
+
+        y [H, W], u and v [H/2, W/2] (H, W >= 2): numpy uint8 → numpy [H, W, 3]; or CUDA uint8 tensors (rows
+        may be strided) → a CUDA tensor, enqueued on this engine's stream and synchronised before returning."""
+        if all(hasattr(p, "is_cuda") and p.is_cuda for p in (y, u, v)):
+            import torch
+
+            for p, name in ((y, "y"), (u, "u"), (v, "v")):
+                if p.dtype != torch.uint8 or p.dim() != 2 or (p.shape[1] > 1 and p.stride(1) != 1):
+                    raise FracError(f"yuv_to_rgb: {name} must be a 2-D uint8 tensor with contiguous rows")
+            H, W = int(y.shape[0]), int(y.shape[1])
+            if tuple(u.shape) != (H // 2, W // 2) or tuple(v.shape) != (H // 2, W // 2):
+                raise FracError(f"yuv_to_rgb: u and v must be {H // 2}x{W // 2}")
+            strides = [_device_rows(p, int(p.shape[1]), "yuv_to_rgb") for p in (y, u, v)]
+            rgb = torch.empty((H, W, 3), dtype=torch.uint8, device=y.device)
+            torch.cuda.current_stream(y.device).synchronize()  # the planes must be ready before our stream reads them
+            self._check(lib().frac_yuv_to_rgb_device(self._ctx, C.c_void_p(y.data_ptr()), W, H, strides[0],
+                                                     C.c_void_p(u.data_ptr()), strides[1], C.c_void_p(v.data_ptr()),
+                                                     strides[2], C.c_void_p(rgb.data_ptr()), 3 * W))
+            self.sync()
+            return rgb
+        if any(hasattr(p, "is_cuda") for p in (y, u, v)):
+            raise FracError("yuv_to_rgb: three numpy arrays or three CUDA tensors")
+        y, u, v = (np.ascontiguousarray(p, dtype=np.uint8) for p in (y, u, v))
+        if y.ndim != 2 or u.shape != (y.shape[0] // 2, y.shape[1] // 2) or v.shape != u.shape:
+            raise FracError("yuv_to_rgb: y must be [H, W], u and v [H/2, W/2]")
+        H, W = y.shape
+        rgb = np.zeros((H, W, 3), np.uint8)
+        self._check(lib().frac_yuv_to_rgb(self._ctx, y.ctypes.data, u.ctypes.data, v.ctypes.data, W, H,
+                                          rgb.ctypes.data, 3 * W))
+        return rgb
+
+    def decode_frc3(self, stream, scale: int = 1, max_iter: int = -1, rms_eps: float = 1e-5, out=None):
+        """An FRC3 colour container to RGB on the GPU (frac_decode_frc3): each plane stream decoded as decode_frc1
+        / decode_frq1 at `scale` from a zero plane, the planes converted on the device, only the RGB copied out.
+        Returns (rgb [scale·H, scale·W, 3], [iterations]·3, [rms]·3).  `out`: a CUDA uint8 tensor of that shape
+        (rows may be strided) receives the pixels on the device (frac_decode_frc3_device) and is returned."""
+        h = frc3_info(stream)
+        k = scale if 1 <= scale <= 16 else 0  # the library refuses the scale; nothing is sized by it
+        W, H = k * h["width"], k * h["height"]
+        buf = np.frombuffer(stream, dtype=np.uint8)
+        it = (C.c_int * 3)()
+        rms = (C.c_double * 3)()
+        if out is not None:
+            import torch
+
+            if not (hasattr(out, "is_cuda") and out.is_cuda) or out.dtype != torch.uint8 or out.dim() != 3:
+                raise FracError("decode_frc3: out must be a CUDA uint8 tensor [H, W, 3]")
+            if tuple(out.shape) != (H, W, 3) or out.stride(2) != 1 or out.stride(1) != 3:
+                raise FracError(f"decode_frc3: out must be {H}x{W}x3 with packed pixels")
+            stride = _device_rows(out, 3 * W, "decode_frc3")
+            torch.cuda.current_stream(out.device).synchronize()  # pending work on `out` lands first
+            self._check(lib().frac_decode_frc3_device(self._ctx, buf.ctypes.data, len(buf), scale, max_iter, rms_eps,
+                                                      C.c_void_p(out.data_ptr()), stride,
+                                                      stride * max(H - 1, 0) + 3 * W, it, rms))
+            self.sync()
+            return out, list(it), list(rms)
+        rgb = np.zeros((H, W, 3), np.uint8)
+        self._check(lib().frac_decode_frc3(self._ctx, buf.ctypes.data, len(buf), scale, max_iter, rms_eps,
+                                           rgb.ctypes.data, 3 * W, rgb.size, it, rms))
+        return rgb, list(it), list(rms)
+
     def device_results_ptr(self) -> int:
         """The device address of the last run's records; 0 when none are readable (no run yet, or a setter
         called since the last one)."""
@@ -728,3 +847,10 @@ def decode_stream(stream, scale: int = 1, device: int = 0, **kw):
         if bytes(memoryview(stream)[:4]) == b"FRQ1":
             return e.decode_frq1(stream, scale, **kw)
         return e.decode_frc1(stream, scale, **kw)
+
+
+def decode_color_stream(stream, scale: int = 1, device: int = 0, **kw):
+    """One call from an FRC3 colour container to RGB pixels, beside decode_stream: Engine.decode_frc3 on a context
+    of its own (kw: max_iter, rms_eps, out).  Returns (rgb, [iterations]·3, [rms]·3)."""
+    with Engine(device) as e:
+        return e.decode_frc3(stream, scale, **kw)

@@ -60,6 +60,23 @@ per level in level order:
 One quantizer pair covers the whole stream, built over every leaf's contrast and brightness as FRC1's.
 frac_decode_frq1 (Engine.decode_frq1) consumes this layout on the device, frac_pack_frq1 writes it from
 32-byte leaves; pack_quadtree_stream / unpack_quadtree_stream are the host restatement.
+
+Colour container layout ("FRC3", little-endian): one colour frame, the three plane streams of a colour
+encode (fractencode_amd.color) in one buffer::
+
+    0   char[4]  magic "FRC3"
+    4   u16      version (1)
+    6   u16      flags (reserved, 0)
+    8   u32      width, height          the RGB frame's; both >= 2 and <= 65535
+    16  u32      len_y, len_u, len_v    bytes of each plane stream
+    28  u32      reserved, 0
+    32  the Y, U, V plane streams in that order, each a complete FRC1 or FRQ1 stream (told apart by its own
+        magic, kinds may be mixed), each zero-padded to a multiple of 8 bytes
+
+The Y stream's frame is width × height, the U and V streams' (width/2) × (height/2), as rgb2yuv makes the
+planes (image/ImageIO.cpp:43-58).  frac_decode_frc3 (Engine.decode_frc3) decodes the three planes on the
+device and converts them to packed RGB there (ImageIO::yuv2rgb, ImageIO.cpp:68-84); frac_pack_frc3 /
+frac_frc3_info write and parse the container; pack_color_stream / unpack_color_stream are the host restatement.
 """
 from __future__ import annotations
 
@@ -446,3 +463,100 @@ def unpack_quadtree_stream(buf: bytes) -> tuple[np.ndarray, dict]:
     rec["brightness"] = np.where(has, deq(np.concatenate([p[3] for p in parts]), h["brightness_min"],
                                           h["brightness_max"], h["brightness_bits"]), 0.0)
     return rec, h
+
+
+# ---- FRC3: the colour container (layout in the module docstring) --------------------------------
+
+COLOR_MAGIC = b"FRC3"
+COLOR_HEADER = struct.Struct("<4sHHIIIIII")
+assert COLOR_HEADER.size == 32
+KIND_FRC1, KIND_FRQ1 = 1, 2
+
+
+def _plane_stream_frame(buf: bytes, name: str) -> tuple[int, int, int]:
+    """(kind, width, height) of a plane stream, which its own unpacker must accept."""
+    magic = bytes(buf[:4])
+    if magic == MAGIC:
+        # frac_frc1_info's rules on the header, which unpack_stream takes on trust
+        h = read_header(buf)
+        if not (h["width"] and h["height"] and h["range_size"]):
+            raise ValueError("FRC1: zero width, height or range size")
+        if h["domain_size"] < 2 or h["domain_size"] % 2 or h["domain_stride"] != h["domain_size"] // 2:
+            raise ValueError("FRC1: domain size must be even and at least 2, its stride half of it")
+        if not 1 <= h["transforms"] <= 8:
+            raise ValueError("FRC1: transforms outside 1..8")
+        if not (2 <= h["contrast_bits"] <= 24 and 2 <= h["brightness_bits"] <= 24):
+            raise ValueError("FRC1: contrast / brightness bits outside [2, 24]")
+        grids = [_grid_cols_rows(h["width"], h["height"], *g) for g in
+                 ((h["range_size"], h["range_size"]), (h["domain_size"], h["domain_stride"]))]
+        if [h["n_ranges"], h["n_domains"]] != [c * r for c, r in grids]:
+            raise ValueError("FRC1: range or domain count is not its grid's")
+        if h["index_bits"] != max(1, int(h["n_domains"]).bit_length()):
+            raise ValueError("FRC1: index bits do not match the domain count")
+        if not all(np.isfinite(h[k]) for k in ("contrast_min", "contrast_max", "brightness_min", "brightness_max")):
+            raise ValueError("FRC1: non-finite quantizer bound")
+        _, h = unpack_stream(buf)
+        kind = KIND_FRC1
+    elif magic == QT_MAGIC:
+        _, h = unpack_quadtree_stream(buf)
+        kind = KIND_FRQ1
+    else:
+        raise ValueError(f"FRC3: the {name} stream is neither an FRC1 nor an FRQ1 stream")
+    return kind, h["width"], h["height"]
+
+
+def _check_color_planes(streams, width: int, height: int) -> list[int]:
+    if not (2 <= width <= 65535 and 2 <= height <= 65535):
+        raise ValueError("FRC3: width and height must be in 2..65535")
+    if len(streams) != 3:
+        raise ValueError("FRC3: three plane streams (Y, U, V)")
+    kinds = []
+    for k, (name, s) in enumerate(zip("YUV", streams)):
+        kind, w, h = _plane_stream_frame(bytes(s), name)
+        want = (width, height) if k == 0 else (width // 2, height // 2)
+        if (w, h) != want:
+            raise ValueError(f"FRC3: the {name} stream's frame is {w}x{h}, the plane's {want[0]}x{want[1]}")
+        kinds.append(kind)
+    return kinds
+
+
+def pack_color_stream(streams, width: int, height: int) -> bytes:
+    """The Y, U and V plane streams (FRC1 or FRQ1, kinds may be mixed) of a width × height RGB frame as one
+    FRC3 container."""
+    streams = [bytes(s) for s in streams]
+    _check_color_planes(streams, width, height)
+    out = COLOR_HEADER.pack(COLOR_MAGIC, VERSION, 0, width, height, *(len(s) for s in streams), 0)
+    for s in streams:
+        out += s + bytes(-len(s) % 8)
+    return out
+
+
+def unpack_color_stream(buf: bytes) -> tuple[list[bytes], dict]:
+    """FRC3 → ([Y, U, V] plane streams without their padding, header dict).  The dict has width, height, flags
+    and, per plane, kind (1 = FRC1, 2 = FRQ1), offset and length (bytes from the start of the container), and
+    total_bytes.  Every plane stream is checked by its own unpacker and against the frame."""
+    buf = bytes(buf)
+    if len(buf) < COLOR_HEADER.size:
+        raise ValueError("FRC3: truncated header")
+    magic, version, flags, width, height, ly, lu, lv, reserved = COLOR_HEADER.unpack_from(buf, 0)
+    if magic != COLOR_MAGIC or version != VERSION:
+        raise ValueError("FRC3: bad magic or version")
+    if flags or reserved:
+        raise ValueError("FRC3: the flags or the reserved word are not zero")
+    if not (2 <= width <= 65535 and 2 <= height <= 65535):
+        raise ValueError("FRC3: width and height must be in 2..65535")
+    h = {"width": width, "height": height, "flags": flags, "kind": [], "offset": [], "length": []}
+    pos, streams = COLOR_HEADER.size, []
+    for n in (ly, lu, lv):
+        padded = n + (-n % 8)
+        if len(buf) - pos < padded:
+            raise ValueError("FRC3: a plane section runs past the end of the stream")
+        if any(buf[pos + n:pos + padded]):
+            raise ValueError("FRC3: a padding byte is not zero")
+        streams.append(buf[pos:pos + n])
+        h["offset"].append(pos)
+        h["length"].append(n)
+        pos += padded
+    h["total_bytes"] = pos
+    h["kind"] = _check_color_planes(streams, width, height)
+    return streams, h

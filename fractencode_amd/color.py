@@ -8,12 +8,15 @@ are enqueued on three engines that share one HIP stream, so the searches run in 
 search alone fills the GPU, and letting the small chroma searches overlap it on streams of their
 own measured slower (C5: 12.73 vs 12.54 ms per frame for the three searches, 13.32 vs 12.69 ms with
 the conversion; profiles/r03/session5/paths.jsonl).  streams="own" keeps one stream per engine.
+
+The way back: pack_frc3 / encode_quadtree_frc3 put the three planes' streams into one FRC3 container
+(codec.py), which Engine.decode_frc3 / decode_color_stream decode to RGB on the device.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from . import ENGINE_AUTO, Engine, create_uniform_grid
+from . import ENGINE_AUTO, Engine, FracError, create_uniform_grid, pack_frc3
 
 PLANES = ("Y", "U", "V")
 
@@ -59,6 +62,7 @@ class ColorEncoder:
             rgb = torch.from_numpy(np.ascontiguousarray(rgb, dtype=np.uint8)).to(f"cuda:{self.device}")
         planes = self.engines[0].rgb_to_yuv(rgb)
         self.planes = planes
+        self.frame_wh = (int(rgb.shape[1]), int(rgb.shape[0]))
         n, d = self.range_size, self.domain_size
         geom = [tuple(p.shape) for p in planes]
         same = geom == getattr(self, "_geom", None)
@@ -109,6 +113,23 @@ class ColorEncoder:
             doms = create_uniform_grid(W, H, self.domain_size, self.domain_size // 2)
             out.append(encode_sharded(e, rngs, doms, rank, world, device=device, group=group))
         return out
+
+    def pack_frc3(self, contrast_bits: int = 5, brightness_bits: int = 7) -> bytes:
+        """After run() and sync(): each engine's pack_frc1 (quantized and packed on the device), the three
+        streams in one FRC3 container."""
+        if self.planes is None:
+            raise FracError("pack_frc3: no frame loaded")
+        return pack_frc3([e.pack_frc1(contrast_bits, brightness_bits) for e in self.engines], *self.frame_wh)
+
+    def encode_quadtree_frc3(self, max_size: int = 16, min_size: int = 4, split_distance: float = 10.0,
+                             contrast_bits: int = 5, brightness_bits: int = 7):
+        """After load(): each engine's encode_quadtree_stream (an FRQ1 stream per plane) in one FRC3 container.
+        Returns (container bytes, [summed stats dict] for Y, U, V)."""
+        if self.planes is None:
+            raise FracError("encode_quadtree_frc3: no frame loaded")
+        parts = [e.encode_quadtree_stream(max_size, min_size, split_distance, contrast_bits, brightness_bits)
+                 for e in self.engines]
+        return pack_frc3([s for s, _ in parts], *self.frame_wh), [st for _, st in parts]
 
     def host_planes(self):
         return [p.cpu().numpy() for p in self.planes]

@@ -1,5 +1,5 @@
-// fracenc_codec.hip — the decoders (items, a run's results, FRC1 streams), the FRC1 packer and parser,
-// and the colour conversion entry points.  Included by fracenc_api.hip.
+// fracenc_codec.hip — the decoders (items, a run's results, FRC1 / FRQ1 streams, FRC3 colour containers), the
+// stream packers and parsers, and the colour conversion entry points.  Included by fracenc_api.hip.
 extern "C" {
 
 int frac_rgb_to_yuv_device(frac_ctx* c, const void* d_rgb, uint32_t w, uint32_t h, uint32_t rgb_stride, void* d_y,
@@ -64,6 +64,76 @@ int frac_rgb_to_yuv(frac_ctx* c, const uint8_t* rgb, uint32_t w, uint32_t h, uin
     return FRAC_OK;
 }
 
+// The conversion back, enqueued on the context's stream, with chroma planes of their own size cw × ch
+// (frac_yuv_to_rgb_device passes w/2 × h/2; a scaled decode of an odd frame has narrower ones).
+static int yuv_to_rgb_launch(frac_ctx* c, const void* d_y, uint32_t w, uint32_t h, uint32_t y_stride, const void* d_u,
+                             uint32_t u_stride, const void* d_v, uint32_t v_stride, uint32_t cw, uint32_t ch,
+                             void* d_rgb, uint32_t rgb_stride)
+{
+    if (w < 2 || h < 2 || cw == 0 || ch == 0)
+        return c->fail(FRAC_E_INVALID, "yuv_to_rgb: a frame below 2 pixels a side has no chroma plane");
+    if (!d_y || !d_u || !d_v || !d_rgb || rgb_stride < 3ull * w || y_stride < w || u_stride < cw || v_stride < cw)
+        return c->fail(FRAC_E_INVALID, "yuv_to_rgb: invalid plane pointers or strides");
+    FRAC_HIP(c, hipSetDevice(c->device));
+    YuvArgs a;
+    a.y = static_cast<const uint8_t*>(d_y);
+    a.w = w;
+    a.h = h;
+    a.ys = y_stride;
+    a.u = static_cast<const uint8_t*>(d_u);
+    a.us = u_stride;
+    a.v = static_cast<const uint8_t*>(d_v);
+    a.vs = v_stride;
+    a.cw = cw;
+    a.ch = ch;
+    a.rgb = static_cast<uint8_t*>(d_rgb);
+    a.rgb_stride = rgb_stride;
+    if (yuv_fast_path(a)) {
+        const size_t n = (size_t)(w / 4) * (h / 2);
+        yuv2rgb_quads4<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(a);
+    } else {
+        const size_t n = (size_t)((w + 1) / 2) * ((h + 1) / 2);
+        yuv2rgb_generic<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(a);
+    }
+    FRAC_HIP(c, hipGetLastError());
+    return FRAC_OK;
+}
+
+int frac_yuv_to_rgb_device(frac_ctx* c, const void* d_y, uint32_t w, uint32_t h, uint32_t y_stride, const void* d_u,
+                           uint32_t u_stride, const void* d_v, uint32_t v_stride, void* d_rgb, uint32_t rgb_stride)
+{
+    if (!c)
+        return FRAC_E_INVALID;
+    return yuv_to_rgb_launch(c, d_y, w, h, y_stride, d_u, u_stride, d_v, v_stride, w / 2, h / 2, d_rgb, rgb_stride);
+}
+
+int frac_yuv_to_rgb(frac_ctx* c, const uint8_t* y, const uint8_t* u, const uint8_t* v, uint32_t w, uint32_t h,
+                    uint8_t* rgb, uint32_t rgb_stride)
+{
+    if (!c)
+        return FRAC_E_INVALID;
+    if (w < 2 || h < 2)
+        return c->fail(FRAC_E_INVALID, "yuv_to_rgb: a frame below 2 pixels a side has no chroma plane");
+    if (!y || !u || !v || !rgb || rgb_stride < 3ull * w)
+        return c->fail(FRAC_E_INVALID, "yuv_to_rgb: invalid buffers");
+    FRAC_HIP(c, hipSetDevice(c->device));
+    const uint32_t cw = w / 2, ch = h / 2;
+    const uint32_t ys = plane_pitch(w), cs = plane_pitch(cw), rs = plane_pitch(3 * w);
+    const size_t y_bytes = (size_t)ys * h, c_bytes = (size_t)cs * ch, rgb_bytes = (size_t)rs * h;
+    FRAC_HIP(c, c->d_color.ensure(rgb_bytes + y_bytes + 2 * c_bytes));
+    uint8_t* d_rgb = c->d_color.ptr;
+    uint8_t* d_y = d_rgb + rgb_bytes;
+    uint8_t* d_u = d_y + y_bytes;
+    uint8_t* d_v = d_u + c_bytes;
+    FRAC_HIP(c, hipMemcpy2DAsync(d_y, ys, y, w, w, h, hipMemcpyHostToDevice, c->stream));
+    FRAC_HIP(c, hipMemcpy2DAsync(d_u, cs, u, cw, cw, ch, hipMemcpyHostToDevice, c->stream));
+    FRAC_HIP(c, hipMemcpy2DAsync(d_v, cs, v, cw, cw, ch, hipMemcpyHostToDevice, c->stream));
+    FRAC_TRY(yuv_to_rgb_launch(c, d_y, w, h, ys, d_u, cs, d_v, cs, cw, ch, d_rgb, rs));
+    FRAC_HIP(c, hipMemcpy2DAsync(rgb, rgb_stride, d_rgb, rs, 3ull * w, h, hipMemcpyDeviceToHost, c->stream));
+    FRAC_HIP(c, hipStreamSynchronize(c->stream));
+    return FRAC_OK;
+}
+
 // Do the items (x, y, w, h) cover the w×h plane exactly once?  Checked on a bitmap of cells of
 // the smallest item size (every item a multiple of it, aligned), so O(cells), not O(pixels).
 static bool covers_exactly(const std::vector<frac_grid_item>& rects, uint32_t w, uint32_t h)
@@ -98,8 +168,39 @@ static bool covers_exactly(const std::vector<frac_grid_item>& rects, uint32_t w,
 // from src and adds its (source − new)² sums to the kDecodeSlots slots (decode_fused over items, frc1dec_step
 // over a stream's records); decode_check, the buffer swap and the host's look at the flag every few steps
 // are shared.
+// Where a decode's plane comes from and goes to.  The initial target is a host plane (stride w) or, absent,
+// zeros; the decoded plane goes to a host plane (stride w; the call returns synchronised) or stays on the
+// device, copied to d_out with its pitch on the context's stream.
+struct PlaneIO {
+    const uint8_t* h_init = nullptr;
+    uint8_t* h_out = nullptr;
+    uint8_t* d_out = nullptr;
+    uint32_t d_pitch = 0;
+    bool valid() const { return h_out || d_out; }
+};
+// the public decoders' plane: host in, host out
+static PlaneIO host_plane(uint8_t* plane)
+{
+    PlaneIO io;
+    io.h_init = io.h_out = plane;
+    return io;
+}
+
+// the decoded plane `fin` (on the device, row pitch `stride`) to its destination
+static int decode_deliver(frac_ctx* c, const PlaneIO& io, const uint8_t* fin, uint32_t stride, uint32_t w, uint32_t h)
+{
+    if (io.h_out) {
+        FRAC_HIP(c, hipMemcpy2DAsync(io.h_out, w, fin, stride, w, h, hipMemcpyDeviceToHost, c->stream));
+        FRAC_HIP(c, hipStreamSynchronize(c->stream));
+    } else {
+        FRAC_TRY(copy_plane(c, io.d_out, io.d_pitch, fin, stride, w, h, hipMemcpyDeviceToDevice, c->stream));
+    }
+    FRAC_HIP(c, hipGetLastError());
+    return FRAC_OK;
+}
+
 extern "C++" template <class Step>
-static int decode_fused_loop(frac_ctx* c, uint32_t w, uint32_t h, int iters, double eps, uint8_t* plane,
+static int decode_fused_loop(frac_ctx* c, uint32_t w, uint32_t h, int iters, double eps, const PlaneIO& io,
                              int* iterations, double* rms, Step&& step)
 {
     const uint32_t stride = plane_pitch(w);
@@ -113,7 +214,8 @@ static int decode_fused_loop(frac_ctx* c, uint32_t w, uint32_t h, int iters, dou
     uint8_t* buf[2] = {c->d_dec_src.ptr, c->d_dec_tgt.ptr};
     FRAC_HIP(c, hipMemsetAsync(buf[0], 100, bytes, c->stream)); // Decoder2: source filled with 100
     FRAC_HIP(c, hipMemsetAsync(buf[1], 0, bytes, c->stream));
-    FRAC_HIP(c, hipMemcpy2DAsync(buf[1], stride, plane, w, w, h, hipMemcpyHostToDevice, c->stream));
+    if (io.h_init)
+        FRAC_HIP(c, hipMemcpy2DAsync(buf[1], stride, io.h_init, w, w, h, hipMemcpyHostToDevice, c->stream));
     FRAC_HIP(c, hipMemsetAsync(c->d_dec_state.ptr, 0, sizeof(DecodeState), c->stream));
     constexpr int kChunk = 8; // iterations enqueued between host checks of the convergence flag
     int enq = 0;
@@ -139,9 +241,7 @@ static int decode_fused_loop(frac_ctx* c, uint32_t w, uint32_t h, int iters, dou
     // the final target: step `it` when the loop broke there, else step iters − 1
     const int last = iters > 0 ? (c->h_dec_state->done ? it : iters - 1) : -1;
     const uint8_t* fin = last >= 0 ? buf[(last + 1) & 1] : buf[1];
-    FRAC_HIP(c, hipMemcpy2DAsync(plane, w, fin, stride, w, h, hipMemcpyDeviceToHost, c->stream));
-    FRAC_HIP(c, hipStreamSynchronize(c->stream));
-    FRAC_HIP(c, hipGetLastError());
+    FRAC_TRY(decode_deliver(c, io, fin, stride, w, h));
     if (iterations)
         *iterations = it;
     if (rms)
@@ -151,13 +251,13 @@ static int decode_fused_loop(frac_ctx* c, uint32_t w, uint32_t h, int iters, dou
 
 // Fused decode (fracenc_decode.hip decode_fused / decode_check): the items tile the plane.
 static int decode_fused_impl(frac_ctx* c, const frac_encode_item* d_items, size_t n, uint32_t w, uint32_t h,
-                             int iters, double eps, uint8_t* plane, int* iterations, double* rms)
+                             int iters, double eps, const PlaneIO& io, int* iterations, double* rms)
 {
     DecodeArgs a;
     a.items = d_items;
     a.n = (uint32_t)n;
     const uint32_t nblk = (uint32_t)((n + 3) / 4);
-    return decode_fused_loop(c, w, h, iters, eps, plane, iterations, rms,
+    return decode_fused_loop(c, w, h, iters, eps, io, iterations, rms,
                              [&](const uint8_t* src, uint8_t* tgt, uint32_t stride) {
                                  a.src = src;
                                  a.tgt = tgt;
@@ -167,13 +267,13 @@ static int decode_fused_impl(frac_ctx* c, const frac_encode_item* d_items, size_
 }
 
 static int decode_impl(frac_ctx* c, const frac_encode_item* d_items, size_t n, uint32_t w, uint32_t h, int max_iter,
-                       double eps, uint8_t* plane, int* iterations, double* rms, bool fused = false)
+                       double eps, const PlaneIO& io, int* iterations, double* rms, bool fused = false)
 {
-    if (!plane || w == 0 || h == 0)
+    if (!io.valid() || w == 0 || h == 0)
         return c->fail(FRAC_E_INVALID, "decode: invalid plane");
     FRAC_TRY(check_ab_knobs(c));
     if (fused &&!(c->p.flags & FRAC_FLAG_DECODE_STEPWISE) && ab_knob("FRAC_DECODE_UNFUSED") == nullptr)
-        return decode_fused_impl(c, d_items, n, w, h, max_iter < 0 ? 300 : max_iter, eps, plane, iterations, rms);
+        return decode_fused_impl(c, d_items, n, w, h, max_iter < 0 ? 300 : max_iter, eps, io, iterations, rms);
     const uint32_t stride = plane_pitch(w);
     const size_t bytes = (size_t)stride * (h + 1);
     FRAC_HIP(c, c->d_dec_src.ensure(bytes));
@@ -183,7 +283,8 @@ static int decode_impl(frac_ctx* c, const frac_encode_item* d_items, size_t n, u
     // Decoder2::decode: source filled with 100, target = the caller's plane
     FRAC_HIP(c, hipMemsetAsync(c->d_dec_src.ptr, 100, bytes, c->stream));
     FRAC_HIP(c, hipMemsetAsync(c->d_dec_tgt.ptr, 0, bytes, c->stream));
-    FRAC_HIP(c, hipMemcpy2DAsync(c->d_dec_tgt.ptr, stride, plane, w, w, h, hipMemcpyHostToDevice, c->stream));
+    if (io.h_init)
+        FRAC_HIP(c, hipMemcpy2DAsync(c->d_dec_tgt.ptr, stride, io.h_init, w, w, h, hipMemcpyHostToDevice, c->stream));
     const int iters = max_iter < 0 ? 300 : max_iter;
     DecodeArgs a;
     a.src = c->d_dec_src.ptr;
@@ -209,9 +310,7 @@ static int decode_impl(frac_ctx* c, const frac_encode_item* d_items, size_t n, u
             break;
         FRAC_HIP(c, hipMemcpyAsync(c->d_dec_src.ptr, c->d_dec_tgt.ptr, bytes, hipMemcpyDeviceToDevice, c->stream));
     }
-    FRAC_HIP(c, hipMemcpy2DAsync(plane, w, c->d_dec_tgt.ptr, stride, w, h, hipMemcpyDeviceToHost, c->stream));
-    FRAC_HIP(c, hipStreamSynchronize(c->stream));
-    FRAC_HIP(c, hipGetLastError());
+    FRAC_TRY(decode_deliver(c, io, c->d_dec_tgt.ptr, stride, w, h));
     if (iterations)
         *iterations = i;
     if (rms)
@@ -254,7 +353,7 @@ int frac_decode(frac_ctx* c, const frac_encode_item* items, size_t n, uint32_t w
         all_domains = all_domains && items[i].match.sw != 0 && items[i].match.sh != 0;
     }
     const bool fused = all_domains && covers_exactly(rects, w, h);
-    return decode_impl(c, c->d_dec_items.ptr, n, w, h, max_iter, rms_eps, plane, iterations, rms, fused);
+    return decode_impl(c, c->d_dec_items.ptr, n, w, h, max_iter, rms_eps, host_plane(plane), iterations, rms, fused);
 }
 
 int frac_decode_results(frac_ctx* c, uint32_t w, uint32_t h, int max_iter, double rms_eps, uint8_t* plane,
@@ -281,7 +380,7 @@ int frac_decode_results(frac_ctx* c, uint32_t w, uint32_t h, int max_iter, doubl
                 break;
             }
     }
-    return decode_impl(c, c->d_out.ptr, nranges(c), w, h, max_iter, rms_eps, plane, iterations, rms, fused);
+    return decode_impl(c, c->d_out.ptr, nranges(c), w, h, max_iter, rms_eps, host_plane(plane), iterations, rms, fused);
 }
 
 int frac_pack_frc1(frac_ctx* c, uint32_t cbits, uint32_t bbits, uint8_t* out, size_t cap, size_t* n_out)
@@ -453,23 +552,12 @@ int frac_frc1_info(const uint8_t* stream, size_t len, struct frac_frc1_info* out
     return rc;
 }
 
-int frac_decode_frc1(frac_ctx* c, const uint8_t* stream, size_t len, uint32_t scale, int max_iter, double rms_eps,
-                     uint8_t* plane, size_t plane_bytes, int* iterations, double* rms)
+// frac_decode_frc1 past its argument checks: the parsed stream `h` (records at stream + 72) decoded at `scale`
+// (checked by the caller) from and to `io`.
+static int decode_frc1_parsed(frac_ctx* c, const Frc1Info& h, const uint8_t* stream, uint32_t scale, int max_iter,
+                              double rms_eps, const PlaneIO& io, int* iterations, double* rms)
 {
-    if (!c)
-        return FRAC_E_INVALID;
-    Frc1Info h;
-    {
-        std::string msg;
-        if (frc1_parse(stream, len, &h, msg) != FRAC_OK)
-            return c->fail(FRAC_E_INVALID, msg);
-    }
-    FRAC_TRY(check_ab_knobs(c));
-    if (scale < 1 || scale > 16 || (uint64_t)scale * h.width > 65535 || (uint64_t)scale * h.height > 65535)
-        return c->fail(FRAC_E_INVALID, "decode_frc1: scale must be in 1..16 and the scaled frame at most 65535 a side");
     const uint32_t W = scale * h.width, H = scale * h.height;
-    if (!plane || plane_bytes < (uint64_t)W * H)
-        return c->fail(FRAC_E_INVALID, "decode_frc1: the plane is smaller than the scaled frame");
     const uint32_t n = h.n_ranges;
     Frc1Layout L{};
     L.n_ranges = n;
@@ -525,7 +613,7 @@ int frac_decode_frc1(frac_ctx* c, const uint8_t* stream, size_t len, uint32_t sc
         a.scale = scale;
         a.rec = c->d_frc_rec.ptr;
         const dim3 grid((W + kFrc1TileW - 1) / kFrc1TileW, (H + kFrc1TileH - 1) / kFrc1TileH);
-        return decode_fused_loop(c, W, H, max_iter < 0 ? 300 : max_iter, rms_eps, plane, iterations, rms,
+        return decode_fused_loop(c, W, H, max_iter < 0 ? 300 : max_iter, rms_eps, io, iterations, rms,
                                  [&](const uint8_t* src, uint8_t* tgt, uint32_t stride) {
                                      a.src = src;
                                      a.tgt = tgt;
@@ -541,7 +629,26 @@ int frac_decode_frc1(frac_ctx* c, const uint8_t* stream, size_t len, uint32_t sc
         frc1dec_expand<<<(n + 255) / 256, 256, 0, c->stream>>>(c->d_frc_rec.ptr, L, scale, c->d_dec_items.ptr);
         FRAC_HIP(c, hipGetLastError());
     }
-    return decode_impl(c, c->d_dec_items.ptr, n, W, H, max_iter, rms_eps, plane, iterations, rms, tiles);
+    return decode_impl(c, c->d_dec_items.ptr, n, W, H, max_iter, rms_eps, io, iterations, rms, tiles);
+}
+
+int frac_decode_frc1(frac_ctx* c, const uint8_t* stream, size_t len, uint32_t scale, int max_iter, double rms_eps,
+                     uint8_t* plane, size_t plane_bytes, int* iterations, double* rms)
+{
+    if (!c)
+        return FRAC_E_INVALID;
+    Frc1Info h;
+    {
+        std::string msg;
+        if (frc1_parse(stream, len, &h, msg) != FRAC_OK)
+            return c->fail(FRAC_E_INVALID, msg);
+    }
+    FRAC_TRY(check_ab_knobs(c));
+    if (scale < 1 || scale > 16 || (uint64_t)scale * h.width > 65535 || (uint64_t)scale * h.height > 65535)
+        return c->fail(FRAC_E_INVALID, "decode_frc1: scale must be in 1..16 and the scaled frame at most 65535 a side");
+    if (!plane || plane_bytes < (uint64_t)scale * h.width * scale * h.height)
+        return c->fail(FRAC_E_INVALID, "decode_frc1: the plane is smaller than the scaled frame");
+    return decode_frc1_parsed(c, h, stream, scale, max_iter, rms_eps, host_plane(plane), iterations, rms);
 }
 
 // ---- FRQ1: the quadtree stream (fractencode_amd/codec.py documents the layout) -------------------
@@ -786,26 +893,21 @@ int frac_pack_frq1(const frac_qt_leaf* leaves, size_t n, uint32_t W, uint32_t H,
     return FRAC_OK;
 }
 
-int frac_decode_frq1(frac_ctx* c, const uint8_t* stream, size_t len, uint32_t scale, int max_iter, double rms_eps,
-                     uint8_t* plane, size_t plane_bytes, int* iterations, double* rms)
+// what frac_decode_frq1 refuses of a parsed stream beyond its parser
+static int frq1_decodable(frac_ctx* c, const Frq1Info& h)
 {
-    if (!c)
-        return FRAC_E_INVALID;
-    Frq1Info h;
-    {
-        std::string msg;
-        if (frq1_parse(stream, len, &h, msg) != FRAC_OK)
-            return c->fail(FRAC_E_INVALID, msg);
-    }
-    FRAC_TRY(check_ab_knobs(c));
-    if (scale < 1 || scale > 16 || (uint64_t)scale * h.width > 65535 || (uint64_t)scale * h.height > 65535)
-        return c->fail(FRAC_E_INVALID, "decode_frq1: scale must be in 1..16 and the scaled frame at most 65535 a side");
-    const uint32_t W = scale * h.width, H = scale * h.height;
-    if (!plane || plane_bytes < (uint64_t)W * H)
-        return c->fail(FRAC_E_INVALID, "decode_frq1: the plane is smaller than the scaled frame");
     for (uint32_t k = 0; k < h.levels; ++k)
         if (h.n_domains[k] >= (1u << 24))
             return c->fail(FRAC_E_INVALID, "decode_frq1: a level with 2^24 or more domains");
+    return FRAC_OK;
+}
+
+// frac_decode_frq1 past its argument checks: the parsed stream `h` (body at stream + 64) decoded at `scale`
+// (checked by the caller) from and to `io`.
+static int decode_frq1_parsed(frac_ctx* c, const Frq1Info& h, const uint8_t* stream, uint32_t scale, int max_iter,
+                              double rms_eps, const PlaneIO& io, int* iterations, double* rms)
+{
+    const uint32_t W = scale * h.width, H = scale * h.height;
     const uint32_t n = h.n_leaves;
     Frq1Layout L{};
     L.n_leaves = n;
@@ -910,7 +1012,7 @@ int frac_decode_frq1(frac_ctx* c, const uint8_t* stream, size_t len, uint32_t sc
         a.map = c->d_frq_map.ptr;
         a.leaves = c->d_frq_leaves.ptr;
         const dim3 grid((W + kFrc1TileW - 1) / kFrc1TileW, (H + kFrc1TileH - 1) / kFrc1TileH);
-        return decode_fused_loop(c, W, H, max_iter < 0 ? 300 : max_iter, rms_eps, plane, iterations, rms,
+        return decode_fused_loop(c, W, H, max_iter < 0 ? 300 : max_iter, rms_eps, io, iterations, rms,
                                  [&](const uint8_t* src, uint8_t* tgt, uint32_t stride) {
                                      a.src = src;
                                      a.tgt = tgt;
@@ -926,7 +1028,236 @@ int frac_decode_frq1(frac_ctx* c, const uint8_t* stream, size_t len, uint32_t sc
         frq1dec_expand<<<(n + 255) / 256, 256, 0, c->stream>>>(c->d_frq_leaves.ptr, L, scale, c->d_dec_items.ptr);
         FRAC_HIP(c, hipGetLastError());
     }
-    return decode_impl(c, c->d_dec_items.ptr, n, W, H, max_iter, rms_eps, plane, iterations, rms, whole);
+    return decode_impl(c, c->d_dec_items.ptr, n, W, H, max_iter, rms_eps, io, iterations, rms, whole);
+}
+
+int frac_decode_frq1(frac_ctx* c, const uint8_t* stream, size_t len, uint32_t scale, int max_iter, double rms_eps,
+                     uint8_t* plane, size_t plane_bytes, int* iterations, double* rms)
+{
+    if (!c)
+        return FRAC_E_INVALID;
+    Frq1Info h;
+    {
+        std::string msg;
+        if (frq1_parse(stream, len, &h, msg) != FRAC_OK)
+            return c->fail(FRAC_E_INVALID, msg);
+    }
+    FRAC_TRY(check_ab_knobs(c));
+    if (scale < 1 || scale > 16 || (uint64_t)scale * h.width > 65535 || (uint64_t)scale * h.height > 65535)
+        return c->fail(FRAC_E_INVALID, "decode_frq1: scale must be in 1..16 and the scaled frame at most 65535 a side");
+    if (!plane || plane_bytes < (uint64_t)scale * h.width * scale * h.height)
+        return c->fail(FRAC_E_INVALID, "decode_frq1: the plane is smaller than the scaled frame");
+    FRAC_TRY(frq1_decodable(c, h));
+    return decode_frq1_parsed(c, h, stream, scale, max_iter, rms_eps, host_plane(plane), iterations, rms);
+}
+
+// ---- FRC3: the colour container (fractencode_amd/codec.py documents the layout) -------------------
+
+using Frc3Info = struct frac_frc3_info; // the plain name is the function's
+static size_t frc3_pad8(size_t n) { return (n + 7) & ~(size_t)7; }
+
+// One plane stream of a container: told apart by its magic, parsed by its own parser, its frame compared with
+// the plane's (the frame itself for Y, half of it either way for U and V).  kind: 1 = FRC1, 2 = FRQ1.
+static int frc3_plane(const uint8_t* s, size_t len, uint32_t k, uint32_t width, uint32_t height, uint32_t* kind,
+                      Frc1Info* h1, Frq1Info* hq, std::string& msg)
+{
+    static const char* const names[3] = {"Y", "U", "V"};
+    auto bad = [&](const std::string& why) {
+        msg = std::string("FRC3: the ") + names[k] + " stream: " + why;
+        return FRAC_E_INVALID;
+    };
+    if (!s)
+        return bad("NULL");
+    uint32_t w = 0, h = 0;
+    std::string inner;
+    if (len >= 4 && std::memcmp(s, "FRC1", 4) == 0) {
+        Frc1Info i;
+        if (frc1_parse(s, len, &i, inner) != FRAC_OK)
+            return bad(inner);
+        *kind = 1, w = i.width, h = i.height;
+        if (h1)
+            *h1 = i;
+    } else if (len >= 4 && std::memcmp(s, "FRQ1", 4) == 0) {
+        Frq1Info i;
+        if (frq1_parse(s, len, &i, inner) != FRAC_OK)
+            return bad(inner);
+        *kind = 2, w = i.width, h = i.height;
+        if (hq)
+            *hq = i;
+    } else {
+        return bad("neither an FRC1 nor an FRQ1 stream");
+    }
+    const uint32_t pw = k ? width / 2 : width, ph = k ? height / 2 : height;
+    if (w != pw || h != ph)
+        return bad("its frame is " + std::to_string(w) + "x" + std::to_string(h) + ", the plane's " +
+                   std::to_string(pw) + "x" + std::to_string(ph));
+    return FRAC_OK;
+}
+
+// The FRC3 header "<4sHHIIIIII" parsed, every section checked against the stream length and every plane
+// stream by its own parser (h1 / hq, optional: the three planes' parsed headers, by kind).
+static int frc3_parse(const uint8_t* s, size_t len, Frc3Info* o, Frc1Info* h1, Frq1Info* hq, std::string& msg)
+{
+    auto bad = [&](const char* why) {
+        msg = std::string("FRC3: ") + why;
+        return FRAC_E_INVALID;
+    };
+    if (!s || !o)
+        return bad("NULL argument");
+    if (len < FRAC_FRC3_HEADER_BYTES)
+        return bad("truncated header");
+    uint16_t version, flags;
+    uint32_t u[6];
+    std::memcpy(&version, s + 4, 2);
+    std::memcpy(&flags, s + 6, 2);
+    std::memcpy(u, s + 8, sizeof(u));
+    if (std::memcmp(s, "FRC3", 4) != 0 || version != 1)
+        return bad("bad magic or version");
+    if (flags || u[5])
+        return bad("the flags or the reserved word are not zero");
+    *o = Frc3Info{};
+    o->width = u[0], o->height = u[1], o->flags = flags;
+    if (o->width < 2 || o->height < 2 || o->width > 65535 || o->height > 65535)
+        return bad("width and height must be in 2..65535");
+    uint64_t pos = FRAC_FRC3_HEADER_BYTES;
+    for (uint32_t k = 0; k < 3; ++k) {
+        const uint64_t n = u[2 + k], padded = (n + 7) & ~7ull;
+        if (len - pos < padded)
+            return bad("a plane section runs past the end of the stream");
+        for (uint64_t i = n; i < padded; ++i)
+            if (s[pos + i])
+                return bad("a padding byte is not zero");
+        o->offset[k] = pos, o->length[k] = n;
+        pos += padded;
+    }
+    o->total_bytes = pos;
+    for (uint32_t k = 0; k < 3; ++k)
+        FRAC_TRY(frc3_plane(s + o->offset[k], (size_t)o->length[k], k, o->width, o->height, &o->kind[k],
+                            h1 ? h1 + k : nullptr, hq ? hq + k : nullptr, msg));
+    return FRAC_OK;
+}
+
+int frac_frc3_info(const uint8_t* stream, size_t len, struct frac_frc3_info* out)
+{
+    std::string msg;
+    const int rc = frc3_parse(stream, len, out, nullptr, nullptr, msg);
+    if (rc != FRAC_OK)
+        g_last_error = msg;
+    return rc;
+}
+
+int frac_pack_frc3(const uint8_t* const planes[3], const size_t lens[3], uint32_t width, uint32_t height, uint8_t* out,
+                   size_t cap, size_t* n_out)
+{
+    auto bad = [&](const std::string& why) {
+        g_last_error = why;
+        return FRAC_E_INVALID;
+    };
+    if (!planes || !lens || !n_out)
+        return bad("pack_frc3: NULL argument");
+    if (width < 2 || height < 2 || width > 65535 || height > 65535)
+        return bad("FRC3: width and height must be in 2..65535");
+    size_t total = FRAC_FRC3_HEADER_BYTES;
+    for (uint32_t k = 0; k < 3; ++k) {
+        if (lens[k] > 0xffffffffull)
+            return bad("pack_frc3: a plane stream of 4 GiB or more");
+        uint32_t kind;
+        std::string msg;
+        if (frc3_plane(planes[k], lens[k], k, width, height, &kind, nullptr, nullptr, msg) != FRAC_OK)
+            return bad(msg);
+        total += frc3_pad8(lens[k]);
+    }
+    *n_out = total;
+    if (!out)
+        return FRAC_OK;
+    std::vector<uint8_t> buf(total, 0);
+    const uint16_t version = 1;
+    const uint32_t u[6] = {width, height, (uint32_t)lens[0], (uint32_t)lens[1], (uint32_t)lens[2], 0u};
+    std::memcpy(buf.data(), "FRC3", 4);
+    std::memcpy(buf.data() + 4, &version, 2);
+    std::memcpy(buf.data() + 8, u, sizeof(u));
+    size_t pos = FRAC_FRC3_HEADER_BYTES;
+    for (uint32_t k = 0; k < 3; ++k) {
+        std::memcpy(buf.data() + pos, planes[k], lens[k]);
+        pos += frc3_pad8(lens[k]);
+    }
+    std::memcpy(out, buf.data(), std::min(cap, total));
+    return FRAC_OK;
+}
+
+// Both decode entry points: the three plane streams decoded on the context's stream into the planes of d_frc3
+// (Y at scale·W × scale·H, U and V at scale·(W/2) × scale·(H/2)), then converted into d_rgb, or (d_rgb NULL)
+// into d_frc3's RGB section, which is copied to h_rgb.
+static int decode_frc3_impl(frac_ctx* c, const uint8_t* stream, size_t len, uint32_t scale, int max_iter,
+                            double rms_eps, void* d_rgb, uint8_t* h_rgb, uint32_t rgb_stride, size_t rgb_bytes,
+                            int* iterations, double* rms)
+{
+    if (!c)
+        return FRAC_E_INVALID;
+    Frc3Info info;
+    Frc1Info h1[3];
+    Frq1Info hq[3];
+    {
+        std::string msg;
+        if (frc3_parse(stream, len, &info, h1, hq, msg) != FRAC_OK)
+            return c->fail(FRAC_E_INVALID, msg);
+    }
+    FRAC_TRY(check_ab_knobs(c));
+    if (scale < 1 || scale > 16 || (uint64_t)scale * info.width > 65535 || (uint64_t)scale * info.height > 65535)
+        return c->fail(FRAC_E_INVALID, "decode_frc3: scale must be in 1..16 and the scaled frame at most 65535 a side");
+    for (uint32_t k = 0; k < 3; ++k)
+        if (info.kind[k] == 2)
+            FRAC_TRY(frq1_decodable(c, hq[k]));
+    const uint32_t W = scale * info.width, H = scale * info.height;
+    const uint32_t cw = scale * (info.width / 2), ch = scale * (info.height / 2);
+    if ((!d_rgb && !h_rgb) || rgb_stride < 3ull * W || rgb_bytes < (uint64_t)rgb_stride * (H - 1) + 3ull * W)
+        return c->fail(FRAC_E_INVALID, "decode_frc3: rgb is NULL, its stride below 3·scale·W, or rgb_bytes short of "
+                                       "the last row");
+    FRAC_HIP(c, hipSetDevice(c->device));
+    const uint32_t ys = plane_pitch(W), cs = plane_pitch(cw), rs = plane_pitch(3 * W);
+    const size_t y_bytes = (size_t)ys * H, c_bytes = (size_t)cs * ch;
+    FRAC_HIP(c, c->d_frc3.ensure(y_bytes + 2 * c_bytes + (d_rgb ? 0 : (size_t)rs * H)));
+    uint8_t* const d_plane[3] = {c->d_frc3.ptr, c->d_frc3.ptr + y_bytes, c->d_frc3.ptr + y_bytes + c_bytes};
+    for (uint32_t k = 0; k < 3; ++k) {
+        PlaneIO io;
+        io.d_out = d_plane[k];
+        io.d_pitch = k ? cs : ys;
+        const uint8_t* s = stream + info.offset[k];
+        int it = 0;
+        double r = 0.0;
+        if (info.kind[k] == 1)
+            FRAC_TRY(decode_frc1_parsed(c, h1[k], s, scale, max_iter, rms_eps, io, &it, &r));
+        else
+            FRAC_TRY(decode_frq1_parsed(c, hq[k], s, scale, max_iter, rms_eps, io, &it, &r));
+        if (iterations)
+            iterations[k] = it;
+        if (rms)
+            rms[k] = r;
+    }
+    if (d_rgb)
+        return yuv_to_rgb_launch(c, d_plane[0], W, H, ys, d_plane[1], cs, d_plane[2], cs, cw, ch, d_rgb, rgb_stride);
+    uint8_t* stage = d_plane[2] + c_bytes;
+    FRAC_TRY(yuv_to_rgb_launch(c, d_plane[0], W, H, ys, d_plane[1], cs, d_plane[2], cs, cw, ch, stage, rs));
+    FRAC_TRY(copy_plane(c, h_rgb, rgb_stride, stage, rs, 3 * W, H, hipMemcpyDeviceToHost, c->stream));
+    FRAC_HIP(c, hipStreamSynchronize(c->stream));
+    return FRAC_OK;
+}
+
+int frac_decode_frc3(frac_ctx* c, const uint8_t* stream, size_t len, uint32_t scale, int max_iter, double rms_eps,
+                     uint8_t* rgb, uint32_t rgb_stride, size_t rgb_bytes, int iterations[3], double rms[3])
+{
+    return decode_frc3_impl(c, stream, len, scale, max_iter, rms_eps, nullptr, rgb, rgb_stride, rgb_bytes, iterations,
+                            rms);
+}
+
+int frac_decode_frc3_device(frac_ctx* c, const uint8_t* stream, size_t len, uint32_t scale, int max_iter,
+                            double rms_eps, void* d_rgb, uint32_t rgb_stride, size_t rgb_bytes, int iterations[3],
+                            double rms[3])
+{
+    if (c && !d_rgb)
+        return c->fail(FRAC_E_INVALID, "decode_frc3_device: d_rgb is NULL");
+    return decode_frc3_impl(c, stream, len, scale, max_iter, rms_eps, d_rgb, nullptr, rgb_stride, rgb_bytes,
+                            iterations, rms);
 }
 
 } // extern "C"

@@ -257,6 +257,9 @@ struct frac_ctx {
     // other); a level's per-dword split ranks; the leaf entries; the fast path's leaf number per min_size cell
     DBuf<uint32_t> d_frq_in, d_frq_nodes[2], d_frq_rank, d_frq_map;
     DBuf<uint4> d_frq_leaves;
+    // frac_decode_frc3: the decoded Y, U and V planes (pitch plane_pitch of each width), which never leave the
+    // device, and after them the host variant's RGB staging rows
+    DBuf<uint8_t> d_frc3;
     // quadtree: the per-level domain grids (geometry only) of the last frame size, by log2(n)
     uint32_t qt_w = 0, qt_h = 0;
     std::vector<frac_grid_item> qt_doms[5];

@@ -161,7 +161,8 @@ const char* frac_last_error(const frac_ctx* ctx);
  * frac_decode_results — returns FRAC_E_STATE, and frac_device_results returns NULL: the old winners are never
  * paired with the new parameters, domain list, ranges or planes.  A setter that fails its own argument checks
  * changes nothing.  frac_set_stream, frac_set_tuple_sink, frac_sync, frac_classify_items, frac_decode,
- * frac_decode_frc1, frac_decode_frq1 and the colour conversion leave the results readable. */
+ * frac_decode_frc1, frac_decode_frq1, frac_decode_frc3, frac_decode_frc3_device and the colour conversions
+ * (frac_rgb_to_yuv, frac_rgb_to_yuv_device, frac_yuv_to_rgb, frac_yuv_to_rgb_device) leave the results readable. */
 int frac_set_params(frac_ctx* ctx, const frac_params* params);
 
 /* Planes are uint8, row-major with the given stride (bytes). Copied to the device.
@@ -315,6 +316,25 @@ int frac_rgb_to_yuv_device(frac_ctx* ctx, const void* d_rgb, uint32_t w, uint32_
 int frac_rgb_to_yuv(frac_ctx* ctx, const uint8_t* rgb, uint32_t w, uint32_t h, uint32_t rgb_stride, uint8_t* y,
                     uint8_t* u, uint8_t* v);
 
+/* ---- frame saver: the conversion back (ImageIO::yuv2rgb, image/ImageIO.cpp:68-84, used by saveImage<3>) ----
+ * These two symbols were added after ABI 9 without changing FRAC_ABI_VERSION: probe for them by name
+ * (dlsym) when the library may be older.
+ *
+ * Y (w×h) and U, V (w/2 × h/2) → packed RGB, bit-exact with the built reference, which contracts every
+ * product into its addition: with u' = u − 128, v' = v − 128, R = clamp(fma(1.402, v', y)),
+ * G = clamp(fma(−0.714, v', fma(−0.344, u', y))), B = clamp(fma(1.772, u', y)).  Pixel (x, y) reads chroma
+ * cell (x/2, y/2), clamped to the chroma plane's last column and row: for an odd w or h the reference reads
+ * one cell past the plane (its stride padding), which is undefined here.  w and h at least 2 (a smaller frame
+ * has no chroma plane: FRAC_E_INVALID, nothing launched).  Every stride is in bytes; rgb_stride too, as
+ * frac_rgb_to_yuv's (the reference's own parameter counts pixels).  _device: all pointers are device
+ * pointers, the work is enqueued on the ctx stream and not synchronised (call frac_sync before reading).
+ * The host variant takes tight planes (strides w and w/2), uploads, converts and downloads. */
+int frac_yuv_to_rgb_device(frac_ctx* ctx, const void* d_y, uint32_t w, uint32_t h, uint32_t y_stride,
+                           const void* d_u, uint32_t u_stride, const void* d_v, uint32_t v_stride, void* d_rgb,
+                           uint32_t rgb_stride);
+int frac_yuv_to_rgb(frac_ctx* ctx, const uint8_t* y, const uint8_t* u, const uint8_t* v, uint32_t w, uint32_t h,
+                    uint8_t* rgb, uint32_t rgb_stride);
+
 /* ---- FRC1 quantized stream, packed on the device --------------------------
  * The reference has no file format; encode_data_statistics (main.cpp:106-140) builds
  * Frac::Quantizerd over the frame's (contrast, brightness) range with 5 / 7 bits
@@ -414,6 +434,50 @@ int frac_pack_frq1(const frac_qt_leaf* leaves, size_t n, uint32_t width, uint32_
  * 2^24 or more domains are refused (as frac_qt_leaf cannot name them). */
 int frac_decode_frq1(frac_ctx* ctx, const uint8_t* stream, size_t len, uint32_t scale, int max_iter,
                      double rms_eps, uint8_t* plane, size_t plane_bytes, int* iterations, double* rms);
+
+/* ---- FRC3: one colour frame — the Y, U and V plane streams in one container, decoded to RGB on the device ----
+ * These four symbols were added after ABI 9 without changing FRAC_ABI_VERSION: probe for them by name
+ * (dlsym) when the library may be older.
+ *
+ * FRC3 (fractencode_amd/codec.py documents the layout) holds, after a 32-byte header with the RGB frame's
+ * width and height and the three lengths, the Y, U and V plane streams in that order, each a complete FRC1
+ * or FRQ1 stream (told apart by its own magic; kinds may be mixed), each zero-padded to a multiple of 8 bytes.
+ * Y is width × height, U and V are (width/2) × (height/2), as frac_rgb_to_yuv makes them.
+ * Offsets are bytes from the start of the container. */
+#define FRAC_FRC3_HEADER_BYTES 32
+struct frac_frc3_info {
+    uint32_t width, height, flags;
+    uint32_t kind[3];                 /* 1 = FRC1, 2 = FRQ1 */
+    uint64_t offset[3], length[3];    /* each plane stream, without its padding */
+    uint64_t total_bytes;             /* header, streams and padding */
+};
+/* Host only, no device and no ctx (message via frac_last_error(NULL)): parse and validate a container, the
+ * three plane streams included.  FRAC_E_INVALID for: len < 32; wrong magic or version; non-zero flags or
+ * reserved word; a width or height outside 2..65535; a plane section (padding included) that runs past len; a
+ * non-zero padding byte; a plane stream that its own parser (frac_frc1_info / frac_frq1_info) refuses, or
+ * whose magic is neither kind; a Y stream whose frame is not width × height; a U or V stream whose frame is
+ * not (width/2) × (height/2).  Trailing bytes are ignored. */
+int frac_frc3_info(const uint8_t* stream, size_t len, struct frac_frc3_info* out);
+/* Host only, no ctx: the three plane streams (Y, U, V) of a width × height RGB frame as one container, refused
+ * for the same reasons.  *n_out = container size; writes min(cap, size) bytes (out may be NULL to query the
+ * size). */
+int frac_pack_frc3(const uint8_t* const planes[3], const size_t lens[3], uint32_t width, uint32_t height,
+                   uint8_t* out, size_t cap, size_t* n_out);
+/* frac_decode_frc1 / frac_decode_frq1 of each plane stream at `scale` from a zero initial plane
+ * (main.cpp:171-173), the three planes kept on the device, converted as frac_yuv_to_rgb_device does and only
+ * the packed RGB copied out: (scale·width) × (scale·height) pixels, rows rgb_stride bytes apart
+ * (>= 3·scale·width), rgb_bytes the buffer's capacity (the last row included, else FRAC_E_INVALID).  Y decodes
+ * to scale·width × scale·height, U and V to scale·(width/2) × scale·(height/2): for an odd width or height
+ * narrower than half the frame, where the conversion's chroma clamp applies.  scale, max_iter and rms_eps as
+ * frac_decode_frc1's; iterations[k] and rms[k] (either may be NULL) are what the single-plane call reports for
+ * plane k.  The container and its plane streams are validated on the host before anything is launched; a
+ * record index out of range inside a plane stream fails the call before rgb is written.
+ * _device: rgb is a device pointer, the conversion is enqueued on the ctx stream and not synchronised. */
+int frac_decode_frc3(frac_ctx* ctx, const uint8_t* stream, size_t len, uint32_t scale, int max_iter, double rms_eps,
+                     uint8_t* rgb, uint32_t rgb_stride, size_t rgb_bytes, int iterations[3], double rms[3]);
+int frac_decode_frc3_device(frac_ctx* ctx, const uint8_t* stream, size_t len, uint32_t scale, int max_iter,
+                            double rms_eps, void* d_rgb, uint32_t rgb_stride, size_t rgb_bytes, int iterations[3],
+                            double rms[3]);
 
 /* ---- host helpers (no device needed) ------------------------------------ */
 /* createUniformGrid (image/partition2.hpp:109-135): returns the item count and

@@ -13,7 +13,7 @@
 //   Quantizer<T>        Frac::Quantizer (encode/Quantizer.hpp:7-45) as the built reference
 //                       computes it (value() with the FMA the compiler contracts)
 //   createUniformGrid / preclassify / encodeQuadtree / decode / decode_frc1 / frc1_info / decode_frq1 / frq1_info /
-//                       pack_frq1 — the C ABI entry points
+//                       pack_frq1 / decode_frc3 / frc3_info — the C ABI entry points
 //   Engine's ABI 8/9 methods: an external HIP stream (void*), the tuple sink and 32-byte tuples,
 //                       frame streaming (setFrameAsync / setFrameDeviceAsync), 32-byte quadtree
 //                       leaves, per-run device times
@@ -23,6 +23,7 @@
 
 #include "fracenc.h"
 
+#include <array>
 #include <atomic>
 #include <cassert>
 #include <cmath>
@@ -96,6 +97,16 @@ inline Frq1Info frq1_info(const uint8_t* stream, size_t len)
 {
     Frq1Info info{};
     if (frac_frq1_info(stream, len, &info) != FRAC_OK)
+        throw Error(std::string("fracenc: ") + frac_last_error(nullptr));
+    return info;
+}
+
+// The same for an FRC3 colour container: the frame, and each plane stream's kind and place (frac_frc3_info).
+using Frc3Info = struct ::frac_frc3_info;
+inline Frc3Info frc3_info(const uint8_t* stream, size_t len)
+{
+    Frc3Info info{};
+    if (frac_frc3_info(stream, len, &info) != FRAC_OK)
         throw Error(std::string("fracenc: ") + frac_last_error(nullptr));
     return info;
 }
@@ -273,6 +284,26 @@ public:
                                        uint32_t scale = 1, int max_iter = -1, double rms_eps = 1e-5)
     {
         return decode_frq1(stream.data(), stream.size(), plane, scale, max_iter, rms_eps);
+    }
+    // An FRC3 colour container to packed RGB (frac_decode_frc3): the three plane streams decoded and converted
+    // on the device; rgb becomes 3·scale·W × scale·H bytes, rows tight.  Per plane (Y, U, V) the iteration
+    // count and the final rms.
+    std::array<std::pair<int, double>, 3> decode_frc3(const uint8_t* stream, size_t len, std::vector<uint8_t>& rgb,
+                                                      uint32_t scale = 1, int max_iter = -1, double rms_eps = 1e-5)
+    {
+        const Frc3Info info = frc3_info(stream, len);
+        const uint32_t k = scale >= 1 && scale <= 16 ? scale : 0; // the library refuses the scale itself
+        rgb.assign((size_t)3 * k * info.width * k * info.height, 0);
+        int it[3] = {0, 0, 0};
+        double rms[3] = {0.0, 0.0, 0.0};
+        check(frac_decode_frc3(ctx_, stream, len, scale, max_iter, rms_eps, rgb.data(), 3 * k * info.width, rgb.size(),
+                               it, rms));
+        return {{{it[0], rms[0]}, {it[1], rms[1]}, {it[2], rms[2]}}};
+    }
+    std::array<std::pair<int, double>, 3> decode_frc3(const std::vector<uint8_t>& stream, std::vector<uint8_t>& rgb,
+                                                      uint32_t scale = 1, int max_iter = -1, double rms_eps = 1e-5)
+    {
+        return decode_frc3(stream.data(), stream.size(), rgb, scale, max_iter, rms_eps);
     }
 
 private:
