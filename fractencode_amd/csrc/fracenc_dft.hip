@@ -170,6 +170,14 @@ constexpr int kDftPrio = 131072;
 // u' + |2Pr| = 4·max(Z_0, Z_2) − Σb²/2 is one rounding of exact operands — the exact-form argument
 // (exact in the exact regime, monotone beyond it) holds unchanged.
 constexpr int64_t kFast6Limit = (1ll << 24) - 1; // 2·R6·D6 + Σb² ≤ this
+// the guard of a tile with guard terms {gx = max 2·D6, gy = max Σb²} as one threshold on the block's R6:
+// R6·gx + gy ≤ kFast6Limit  ⇔  gy ≤ kFast6Limit and R6 ≤ ⌊(kFast6Limit − gy) / gx⌋  (−1: no block passes)
+__device__ inline int32_t dft_fast6_rmax(uint32_t gx, uint32_t gy)
+{
+    return (int64_t)gy > kFast6Limit ? -1
+           : gx == 0                  ? INT32_MAX
+                                      : (int32_t)min<int64_t>((kFast6Limit - gy) / gx, INT32_MAX);
+}
 
 // the form the SEA engine's tiled search (fracenc_tp.hip) runs: 4 or 6
 constexpr int kDftTpForm = 6;
@@ -195,6 +203,8 @@ struct DftArgs {
                            // with a chunk's word tile | tile mask << 28 (fracenc_tp.hip)
     const int32_t* trmax;  // kDftFast6: [ntiles] the largest block R6 whose guard holds against the
                            // tile, (kFast6Limit − max Σb²) / max 2·D6 (−1: none)
+    const uint32_t* order = nullptr; // CHUNKED: [workgroups] the work item each workgroup takes (null: its own
+                                     // index) — the windows longest first (tp_plan, fracenc_tp.hip)
     unsigned long long* stamps = nullptr; // FRAC_CLOCK_STAMP builds only: [workgroups][kClockStampWords]
     // not CHUNKED: per range slot the maximum over every work item, merged here with one 64-bit atomicMax per
     // (slot, work item) instead of per-work-item entries: fmap(y) << 32 | (kSlotBestTileMax − chunk) << 6 |
@@ -214,7 +224,9 @@ constexpr uint32_t kClockStampWords = 6;
 // (SamplerBilinear's integer sum, image/sampler.h:21-38, as pool_build), two cells per
 // 32-bit word — (w & 0x00ff00ff) + ((w >> 8) & 0x00ff00ff) over the word of both rows is
 // the packed u16 pair the pool stores — and the same registers feed the tile fragments.
-// Outputs: the pool and −ΣD4² (read by fit_winner and fallback_grid), the pool rows again in
+// Outputs: the pool and −ΣD4² (read by fit_winner and fallback_grid; on the tiled form's route, whose fit is
+// fused into its resolve, only by fallback_grid — not storing them there measured too little: DESIGN §7.10), the
+// pool rows again in
 // tile order (resolve_dft); per 32-domain tile the A fragments of the four K-steps
 // [s_b | u_b | γ | δ] (lane l: row l&31, orbit 8(l>>5) + j), −Σb² per row in the [2][16]
 // lane-half layout of the epilogue, and the tile's fast-path guard terms.  Every pool
@@ -365,12 +377,9 @@ __device__ __forceinline__ void dft_domain_build_at(uint32_t tid, const MfmaDoma
     }
     if (row == 0) {
         tguard[tile] = make_uint2(gx, gy);
-        // the six-MFMA fast path's guard as one threshold on the block's R6:
-        // R6·gx + gy ≤ kFast6Limit  ⇔  gy ≤ kFast6Limit and R6 ≤ ⌊(kFast6Limit − gy) / gx⌋
+        // the six-MFMA fast path's guard as one threshold on the block's R6
         if (F5 && trmax)
-            trmax[tile] = (int64_t)gy > kFast6Limit ? -1
-                          : gx == 0                  ? INT32_MAX
-                                                     : (int32_t)min<int64_t>((kFast6Limit - gy) / gx, INT32_MAX);
+            trmax[tile] = dft_fast6_rmax(gx, gy);
     }
 }
 
@@ -383,7 +392,8 @@ __device__ __forceinline__ void dft_domain_build_at(uint32_t tid, const MfmaDoma
 // A tile's 32 rows are one wave's 64 lanes, so the tile guards stay a wave reduction.
 // BYPOS (the SEA tiled form, as dft_domain_build_at's): the lane pair takes a pool position in domain order and
 // scatters the tile-order outputs to its row (row_of); a tile's rows are then in many waves, so the guards are
-// raised with atomics over the zeroes tp_build wrote (no padding row comes here, and no trmax).
+// raised with atomics over the zeroes tp_build wrote (no padding row comes here, and no trmax: the tiled form's
+// thresholds are formed from the finished guards by tp_seed_windows, fracenc_tp.hip).
 constexpr uint32_t kDbRowWords = 33; // LDS words per row: 32 + 1 of padding (rows in distinct banks)
 template <bool F5, bool BYPOS = false>
 __device__ __forceinline__ void dft_domain_build_pair_at(uint32_t tid2, const MfmaDomainPrepArgs& a,
@@ -515,9 +525,7 @@ __device__ __forceinline__ void dft_domain_build_pair_at(uint32_t tid2, const Mf
     if (row == 0 && hh == 0) {
         tguard[tile] = make_uint2(gx, gy);
         if (F5 && trmax)
-            trmax[tile] = (int64_t)gy > kFast6Limit ? -1
-                          : gx == 0                  ? INT32_MAX
-                                                     : (int32_t)min<int64_t>((kFast6Limit - gy) / gx, INT32_MAX);
+            trmax[tile] = dft_fast6_rmax(gx, gy);
     }
 }
 
@@ -1280,7 +1288,9 @@ __global__ void __launch_bounds__(64 * WAVES) search_dft(DftArgs d)
     if constexpr (DftForm<VAR>::FAST6)
         if (threadIdx.x < 2 * ZTAIL)
             (threadIdx.x < ZTAIL ? lds0 : lds1)[STAGE + (threadIdx.x % ZTAIL)] = make_uint4(0u, 0u, 0u, 0u);
-    const uint4 wk = a.work[blockIdx.x];
+    // (everything below is indexed by the work item's blocks and tiles; blockIdx.x itself only by the
+    // not-CHUNKED entries)
+    const uint4 wk = a.work[(CHUNKED && d.order) ? d.order[blockIdx.x] : blockIdx.x];
     const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const bool active = wv < wk.y;
     const uint32_t blk = wk.x + (active ? wv : 0u);

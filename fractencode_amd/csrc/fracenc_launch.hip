@@ -820,10 +820,10 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
     da.m = search_args(c, c->d_tp_work.ptr, ng); // (host-planned only: no plan)
     da.rguard = c->d_dft_rguard.ptr;
     da.tguard = c->d_dft_tguard.ptr;
-    da.trmax = nullptr; // kTpVar runs the exact epilogue only
+    da.trmax = nullptr; // the seed search runs the exact epilogue (kTpSeedVar); the windowed search's below
     // seed: the Fourier search over one tile per group, into the records the windowed search writes again
     da.rec = c->d_tp_rec.ptr;
-    search_dft<false, kTpVar, W8, 4, true><<<ng, 64 * W8, 0, c->stream>>>(da);
+    search_dft<false, kTpSeedVar, W8, 4, true><<<ng, 64 * W8, 0, c->stream>>>(da);
     // per group: its blocks' seed bounds, then its window
     TpWindowArgs w;
     w.groups = c->d_tp_groups.ptr;
@@ -840,12 +840,18 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
     w.bk = c->tp_bk;
     w.evals = c->d_tp_evals.ptr;
     w.sevals = c->d_tp_sevals.ptr;
+    if (kTpFast) { // the windowed search's guard thresholds, from the tile guards tp_prep finished
+        w.tguard = c->d_dft_tguard.ptr;
+        w.trmax = c->d_dft_trmax.ptr;
+        w.ntiles = nt;
+    }
     tp_seed_windows<<<ng, 256, 0, c->stream>>>(w);
     // the totals (the searched pairs and evaluations) written straight into the host's pinned block
     void* dtot = nullptr;
     FRAC_HIP(c, hipHostGetDevicePointer(&dtot, c->h_tp_tot.ptr, 0));
     tp_plan<<<1, kTpPlanThreads, 0, c->stream>>>(ng, c->d_tp_pairs.ptr, c->d_tp_evals.ptr, c->d_tp_sevals.ptr,
-                                                 reinterpret_cast<uint32_t*>(dtot));
+                                                 reinterpret_cast<uint32_t*>(dtot),
+                                                 kTpLongestFirst ? c->d_tp_order.ptr : nullptr);
     FRAC_HIP(c, hipStreamSynchronize(c->stream));
     uint32_t tot[8];
     for (int k = 0; k < 8; ++k)
@@ -873,6 +879,8 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
     // (padding slots and rows of partial blocks and tiles are no pairs)
     c->flops_ran += pairs * (kDftTpForm == 6 ? 6ull : 8ull) * 32768ull;
     c->evaluated_ran += (uint64_t)tot[4] | ((uint64_t)tot[5] << 32);
+    da.trmax = kTpFast ? c->d_dft_trmax.ptr : nullptr;
+    da.order = kTpLongestFirst ? c->d_tp_order.ptr : nullptr; // the longest windows first (tp_plan)
     launch_search_dft<kTpVar, W8, 4, true>(c, da, ng, c->hitH > 0);
     if (timing)
         FRAC_TRY(mark_event(c, 2));

@@ -110,15 +110,20 @@ inline bool dft_four_wave(int var)
 }
 // the Fourier form's domain/range fragment layout: 4 (8 MFMA per tile pair), 5 (kDft5, variants 20, 22),
 // 6 (kDft6, variants 21, 23)
-constexpr int kTpVar = 1 | kDftChain | (kDftTpForm == 6 ? kDft6 : 0); // the SEA tiled form's search_dft
+// the SEA tiled form's search_dft: the seed search (one tile per group) keeps the exact epilogue; the windowed
+// search runs the exhaustive search's tuned variant (35: kDftFast6 | kDftUnroll | kDftBufDma) when kTpFastSearch
+constexpr int kTpSeedVar = 1 | kDftChain | (kDftTpForm == 6 ? kDft6 : 0);
+constexpr bool kTpFast = kTpFastSearch && kDftTpForm == 6;
+constexpr int kTpVar = kTpFast ? (kTpSeedVar | kDftFast6 | kDftUnroll | kDftBufDma) : kTpSeedVar;
 constexpr uint32_t kTpKS = kDftTpForm == 4 ? 4u : 5u;                    // its domain fragments per tile
 // FRAC_ENGINE_AUTO's pruned route (n = 8, T = 4, ratio 2; DESIGN §4.4, measured in §7.4).
 // kAutoPruneMinPairs: the fewest block × tile pairs (every window open) at which AUTO tries the bound; below
 // it the route's fixed cost — the two sides' sort, about ten small launches, one host turnaround — is too large a
 // share of the run to risk on unknown data (FRAC_FLAG_PRUNE ignores it).
-// kAutoPruneBudget: the share of those pairs the windows may hold; above it the windowed search with its exact
-// epilogue and its resolve costs what the exhaustive search does, and the run falls back to that.  (It bounds
-// time only: the windowed search's records are sized by the layout, not by the windows)
+// kAutoPruneBudget: the share of those pairs the windows may hold; above it the windowed search with its
+// resolve costs what the exhaustive search does, and the run falls back to that.  (It bounds time only: the
+// windowed search's records are sized by the layout, not by the windows; DESIGN §7.7.  The table behind it was
+// measured with the windowed search's exact epilogue, before kTpVar took the guarded fast one, §7.10.)
 // Measured (tools/auto_prune_sweep.py, profiles/r08/auto_prune/): a run forced to fall back costs 0.25 – 0.40 ms
 // more than the exhaustive one end to end — 13.5 % at 8.4 M pairs, 8.4 % at 16.7 M (4096², a quarter of the
 // ranges), 3.2 % at 66.9 M — so the 10 % line lies between the first two and the minimum sits just under the
@@ -763,6 +768,8 @@ int fill_tp(frac_ctx* c, const PrepBuckets& B)
     FRAC_HIP(c, c->d_m_rfrags.ensure(nbk * 7 * 64));
     FRAC_HIP(c, c->d_m_rconst.ensure(nbk * 32));
     FRAC_HIP(c, c->d_dft_tguard.ensure(nt));
+    FRAC_HIP(c, c->d_dft_trmax.ensure(nt + 4)); // + 4: a chunk's thresholds are one scalar load (tp_seed_windows)
+    FRAC_HIP(c, c->d_tp_order.ensure(ng));
     FRAC_HIP(c, c->d_dft_tpool.ensure(nt * 32 * 32));
     FRAC_HIP(c, c->d_dft_rguard.ensure(nbk));
     FRAC_HIP(c, c->d_tp_work.ensure(ng));

@@ -33,6 +33,16 @@ constexpr int kTpMaxBuckets = 8;
 // tp_prep's domain half: two lanes per pool position (dft_domain_build_pair_at, BYPOS), or one
 // (dft_domain_build_at); DESIGN §7.4 has the two times
 constexpr bool kTpPairBuild = true;
+// DESIGN §7.10, each measured alone against its absence:
+// kTpFastSearch: the windowed search runs the exhaustive search's tuned variant (the guarded constant-folded
+//   epilogue, the unrolled chunk, wave-uniform buffer_load … lds stages), its per-tile thresholds written by
+//   tp_seed_windows from the guards tp_prep finished; false: the exact epilogue, as the seed search
+// kTpLongestFirst: the windowed search's workgroups take the groups by window size, longest first (tp_plan's
+//   order); false: in ΣR order, which leaves the longest windows to the middle of the launch
+// (A third, tp_prep storing neither the pool nor −ΣD4² — only the fp32 fallback reads them on this route — took
+// 0.0035 ms off prep, within the lines' spread, and was taken out.)
+constexpr bool kTpFastSearch = true;
+constexpr bool kTpLongestFirst = true;
 
 struct TpBuckets {
     uint32_t nb;
@@ -327,6 +337,11 @@ struct TpWindowArgs {
     TpBuckets bk;
     unsigned long long* evals; // [ngroups] (range, domain) pairs in the window (frac_stats.evaluated_mappings)
     unsigned long long* sevals; // [ngroups] (range, domain) pairs of the seed tile, read from work (tp_prep)
+    // kTpFastSearch: the fast epilogue's per-tile thresholds (DftArgs::trmax) from the tiles' finished guards, with
+    // the four entries of padding a chunk's one scalar load may touch; null: not written
+    const uint2* tguard = nullptr;
+    int32_t* trmax = nullptr;
+    uint32_t ntiles = 0;
 };
 
 // one group's window from its blocks' seed bounds (su), with the sums the totals are made of; one thread
@@ -380,9 +395,20 @@ __device__ __forceinline__ void tp_seed_window_at(const TpWindowArgs& a, uint32_
 
 // tp_seed_windows: one workgroup per group.  Each 32-lane row reduces the seed search's records of one block of
 // the group to its bound (tp_seed_reduce_row) and writes blk_u; one thread then sets the group's window.
+// The grid also shares out the windowed search's guard thresholds (TpWindowArgs::trmax): tp_prep raised the tile
+// guards with atomics, so they are final only now, and the seed search (exact epilogue) did not need them.
 __global__ void __launch_bounds__(256) tp_seed_windows(TpWindowArgs a)
 {
     __shared__ uint32_t su[kDftBlocksPerWG];
+    if (a.trmax)
+        for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < a.ntiles + 4u; t += gridDim.x * blockDim.x) {
+            int32_t v = -1; // (padding: masked out by dft_guard_bits)
+            if (t < a.ntiles) {
+                const uint2 g = a.tguard[t];
+                v = dft_fast6_rmax(g.x, g.y);
+            }
+            a.trmax[t] = v;
+        }
     const uint32_t gi = blockIdx.x;
     const uint4 gr = a.groups[gi];
     {
@@ -404,17 +430,32 @@ __global__ void __launch_bounds__(256) tp_seed_windows(TpWindowArgs a)
 // synchronisation).  The first two words once held the chunk and entry-link counts; nothing is sized from the
 // windows now, and no scan is left.  (Summing them in tp_seed_windows' last workgroup instead — a device-scope
 // fence and a counter per group — saved the launch and measured 0.02 ms slower at C3: DESIGN §7.7.)
+// order (kTpLongestFirst; null: none): the groups by pairs[g] descending in kTpOrderClasses classes of equal width
+// up to the largest, by group index within a class — a stable counting sort, so the order is deterministic and
+// equal windows keep the identity.  The windowed search's workgroup n takes group order[n]: the hardware hands
+// workgroups to the first free place, which with the longest first is the list-scheduling rule (§7.10).
+// Thread t counts the classes of its own run of ⌈ngroups / 256⌉ consecutive groups in its own column of cnt
+// (class-major, so the flattened [class][thread] order is the output order), the columns are scanned in place —
+// thread t taking kTpOrderClasses consecutive counters, padded against bank conflicts — and each thread places
+// its groups from its counters.
 constexpr uint32_t kTpPlanThreads = 256;
+constexpr uint32_t kTpOrderClasses = 32;
 
 __global__ void __launch_bounds__(kTpPlanThreads) tp_plan(uint32_t ngroups, const uint32_t* __restrict__ pairs,
                                                           const unsigned long long* __restrict__ evals,
                                                           const unsigned long long* __restrict__ sevals,
-                                                          uint32_t* __restrict__ tot)
+                                                          uint32_t* __restrict__ tot, uint32_t* __restrict__ order)
 {
-    __shared__ unsigned long long part[3][kTpPlanThreads / 64];
+    constexpr uint32_t NT = kTpPlanThreads, NC = kTpOrderClasses, NW = NT / 64;
+    __shared__ unsigned long long part[3][NW];
+    __shared__ uint32_t pmax[NW], wsum[NW];
+    __shared__ uint32_t cnt[NC * NT + NC * NT / 32];
     unsigned long long s = 0, v = 0, q = 0;
-    for (uint32_t g = threadIdx.x; g < ngroups; g += kTpPlanThreads) {
-        s += pairs[g];
+    uint32_t pm = 0;
+    for (uint32_t g = threadIdx.x; g < ngroups; g += NT) {
+        const uint32_t pg = pairs[g];
+        s += pg;
+        pm = max(pm, pg);
         v += evals[g];
         q += sevals[g];
     }
@@ -423,16 +464,18 @@ __global__ void __launch_bounds__(kTpPlanThreads) tp_plan(uint32_t ngroups, cons
         s += __shfl_xor(s, o, 64);
         v += __shfl_xor(v, o, 64);
         q += __shfl_xor(q, o, 64);
+        pm = max(pm, (uint32_t)__shfl_xor((int)pm, o, 64));
     }
     if ((threadIdx.x & 63u) == 0) {
         part[0][threadIdx.x >> 6] = s;
         part[1][threadIdx.x >> 6] = v;
         part[2][threadIdx.x >> 6] = q;
+        pmax[threadIdx.x >> 6] = pm;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         unsigned long long t = 0, e = 0, se = 0;
-        for (uint32_t k = 0; k < kTpPlanThreads / 64; ++k) {
+        for (uint32_t k = 0; k < NW; ++k) {
             t += part[0][k];
             e += part[1][k];
             se += part[2][k];
@@ -446,6 +489,43 @@ __global__ void __launch_bounds__(kTpPlanThreads) tp_plan(uint32_t ngroups, cons
         tot[6] = (uint32_t)se;
         tot[7] = (uint32_t)(se >> 32);
     }
+    if (!order)
+        return;
+    for (uint32_t k = 0; k < NW; ++k)
+        pm = max(pm, pmax[k]);
+    // class 0 holds the largest windows, class NC − 1 the empty ones
+    auto cls = [&](uint32_t pg) { return NC - 1u - (uint32_t)(((uint64_t)pg * NC) / ((uint64_t)pm + 1u)); };
+    auto at = [](uint32_t i) { return i + (i >> 5); }; // one word of padding per 32
+    const uint32_t per = (ngroups + NT - 1) / NT;
+    const uint32_t g0 = min(threadIdx.x * per, ngroups), g1 = min(g0 + per, ngroups);
+    for (uint32_t c = 0; c < NC; ++c)
+        cnt[at(c * NT + threadIdx.x)] = 0u;
+    for (uint32_t g = g0; g < g1; ++g)
+        ++cnt[at(cls(pairs[g]) * NT + threadIdx.x)];
+    __syncthreads();
+    uint32_t mine = 0;
+    for (uint32_t k = 0; k < NC; ++k)
+        mine += cnt[at(threadIdx.x * NC + k)];
+    uint32_t inc = mine; // the inclusive scan over the workgroup's threads
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t up = (uint32_t)__shfl_up((int)inc, o, 64);
+        inc += (threadIdx.x & 63u) >= (uint32_t)o ? up : 0u;
+    }
+    if ((threadIdx.x & 63u) == 63u)
+        wsum[threadIdx.x >> 6] = inc;
+    __syncthreads();
+    uint32_t run = inc - mine;
+    for (uint32_t k = 0; k < (threadIdx.x >> 6); ++k)
+        run += wsum[k];
+    for (uint32_t k = 0; k < NC; ++k) {
+        const uint32_t i = at(threadIdx.x * NC + k), n = cnt[i];
+        cnt[i] = run;
+        run += n;
+    }
+    __syncthreads();
+    for (uint32_t g = g0; g < g1; ++g)
+        order[cnt[at(cls(pairs[g]) * NT + threadIdx.x)]++] = g;
 }
 
 } // namespace fracenc
