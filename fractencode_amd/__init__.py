@@ -254,6 +254,10 @@ def lib() -> C.CDLL:
             "frac_hit_limit": (C.c_int64, [C.c_double, u32]),
             "frac_debug_sort_chunk": (u32, []),
             "frac_debug_sort_pairs": (i32, [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp, vp]),
+            "frac_debug_bucket_tile": (u32, []),
+            "frac_debug_bucket_self_tiles": (u32, []),
+            "frac_debug_bucket_keys": (i32, [vp, vp, u32, vp, u32, i32, vp, vp]),
+            "frac_debug_bucket_sort": (i32, [vp, u32, u32, vp, u32, u32, vp, vp, vp, vp]),
         }
         for name, (res, args) in sig.items():
             if os.environ.get("FRAC_LIB") and not hasattr(L, name):
@@ -304,6 +308,49 @@ def debug_sort_pairs(keys, vals, keys_b, vals_b, bits: int):
     if rc != 0:
         raise FracError(f"frac_debug_sort_pairs: {last_error()} (code {rc})")
     return tuple(outs)
+
+
+BK_TILE = 1024        # items per workgroup of the classifier bucket sort (frac_debug_bucket_tile)
+BK_SELF_TILES = 512   # the most tiles of a sort without the scan launch (frac_debug_bucket_self_tiles)
+BK_KEYS = 8           # keys 0..7: categories -1..5 and the padding key
+KEYS_AUTO, KEYS_ROWS, KEYS_PAIR, KEYS_BLOCK_SUMS = 0, 1, 2, 3  # frac_debug_bucket_keys' path
+
+
+def debug_bucket_keys(engine, doms, rngs, path: int = KEYS_AUTO):
+    """Test hook: the classifier bucket keys (category + 1) of two GRID_ITEM arrays by the key kernels a
+    classified run uses, the domains on the engine's source plane and the ranges on its target plane.  path:
+    KEYS_AUTO the run's own choice, KEYS_ROWS the row kernels grid by grid, KEYS_PAIR the paired launch,
+    KEYS_BLOCK_SUMS the planes' block sums.  Returns (dom_keys, rng_keys); FracError where the hook refuses."""
+    doms = np.ascontiguousarray(doms, dtype=GRID_ITEM)
+    rngs = np.ascontiguousarray(rngs, dtype=GRID_ITEM)
+    kd, kr = np.full(len(doms), 0xFFFFFFFF, np.uint32), np.full(len(rngs), 0xFFFFFFFF, np.uint32)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
+    rc = lib().frac_debug_bucket_keys(engine._ctx, ptr(doms), len(doms), ptr(rngs), len(rngs), path, ptr(kd), ptr(kr))
+    if rc != 0:
+        raise FracError(f"frac_debug_bucket_keys: {last_error(engine._ctx)} (code {rc})")
+    return kd, kr
+
+
+def debug_bucket_sort(keys_a, keys_b, dn_a: int | None = None, dn_b: int | None = None):
+    """Test hook: the stable bucket sort of two uint32 key arrays (keys 0..7, either may be empty) through the
+    same launches.  dn_*: a count the kernels read on the device (the first min(dn, n) keys are sorted), None
+    for none.  Returns (order_a, first_a, order_b, first_b): the sorted indices, 0xffffffff where the sort
+    wrote nothing, and the BK_KEYS + 1 bucket starts."""
+    L = lib()
+    if L.frac_debug_bucket_tile() != BK_TILE or L.frac_debug_bucket_self_tiles() != BK_SELF_TILES:
+        raise FracError("BK_TILE / BK_SELF_TILES differ from the library's")
+    ka, kb = (np.ascontiguousarray(a, dtype=np.uint32) for a in (keys_a, keys_b))
+    if ka.ndim != 1 or kb.ndim != 1:
+        raise ValueError("keys must be one-dimensional")
+    oa, ob = np.zeros(ka.size, np.uint32), np.zeros(kb.size, np.uint32)
+    fa, fb = np.zeros(BK_KEYS + 1, np.uint32), np.zeros(BK_KEYS + 1, np.uint32)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
+    none = 0xFFFFFFFF
+    rc = L.frac_debug_bucket_sort(ptr(ka), ka.size, none if dn_a is None else dn_a, ptr(kb), kb.size,
+                                  none if dn_b is None else dn_b, ptr(oa), ptr(fa), ptr(ob), ptr(fb))
+    if rc != 0:
+        raise FracError(f"frac_debug_bucket_sort: {last_error()} (code {rc})")
+    return oa, fa, ob, fb
 
 
 # ---- host helpers ----------------------------------------------------------------

@@ -206,6 +206,163 @@ int frac_debug_sort_pairs(const uint32_t* keys, const uint32_t* vals, uint32_t n
     return FRAC_OK;
 }
 
+uint32_t frac_debug_bucket_tile(void) { return kBkTile; }
+uint32_t frac_debug_bucket_self_tiles(void) { return kBkSelfTiles; }
+
+// Test hook: the classifier keys of two host item arrays by the key kernels of fracenc_bucket.hip, the domains on
+// the context's source plane and the ranges on its target plane.  Everything is checked on the host before the
+// first launch; the items and keys live in buffers of the call's own, so the context's prepared state stays as
+// it is (the planes' block sums are scratch that every run rebuilds).
+int frac_debug_bucket_keys(frac_ctx* c, const frac_grid_item* doms, uint32_t nd, const frac_grid_item* rngs, uint32_t nr,
+                           int path, uint32_t* dom_keys, uint32_t* rng_keys)
+{
+    if (!c)
+        return FRAC_E_INVALID;
+    if (!c->planes_set)
+        return c->fail(FRAC_E_INVALID, "debug_bucket_keys: no frame set");
+    if (path < 0 || path > 3)
+        return c->fail(FRAC_E_INVALID, "debug_bucket_keys: path must be 0..3");
+    if ((nd && !(doms && dom_keys)) || (nr && !(rngs && rng_keys)))
+        return c->fail(FRAC_E_INVALID, "debug_bucket_keys: NULL array");
+    const frac_grid_item* items[2] = {doms, rngs};
+    const uint32_t cnt[2] = {nd, nr};
+    const frac_ctx::PlaneSize size[2] = {c->src, c->same_plane ? c->src : c->tgt};
+    uint32_t w[2] = {0, 0}, h[2] = {0, 0}; // the grids' item sizes: the first item's
+    bool one_size = true;
+    for (int s = 0; s < 2; ++s) {
+        if (cnt[s]) {
+            w[s] = items[s][0].w;
+            h[s] = items[s][0].h;
+        }
+        for (uint32_t i = 0; i < cnt[s]; ++i) {
+            const frac_grid_item& it = items[s][i];
+            if ((uint64_t)it.x + it.w > size[s].w || (uint64_t)it.y + it.h > size[s].h)
+                return c->fail(FRAC_E_INVALID, "debug_bucket_keys: item outside the plane");
+            if (it.category < -1 || it.category > 5)
+                return c->fail(FRAC_E_INVALID, "item category outside -1..5");
+            one_size = one_size && it.w == w[s] && it.h == h[s];
+        }
+    }
+    const bool sums = path == 3 || (path == 0 && w[0] <= 32 && h[0] <= 32 && w[1] <= 32 && h[1] <= 32);
+    if (!sums && !one_size) // the row kernels size their lane groups by the grid's first item
+        return c->fail(FRAC_E_INVALID, "debug_bucket_keys: a grid of more than one item size");
+    FRAC_HIP(c, hipSetDevice(c->device));
+    DBuf<frac_grid_item> d_items[2];
+    DBuf<uint32_t> d_keys[2], d_err;
+    FRAC_HIP(c, d_err.ensure(1));
+    FRAC_HIP(c, hipMemsetAsync(d_err.ptr, 0, sizeof(uint32_t), c->stream));
+    for (int s = 0; s < 2; ++s) {
+        FRAC_HIP(c, d_items[s].ensure(cnt[s]));
+        FRAC_HIP(c, d_keys[s].ensure(cnt[s]));
+        if (cnt[s])
+            FRAC_HIP(c, hipMemcpyAsync(d_items[s].ptr, items[s], (size_t)cnt[s] * sizeof(frac_grid_item),
+                                       hipMemcpyHostToDevice, c->stream));
+    }
+    int rc = FRAC_OK;
+    hipError_t e = hipSuccess;
+    {
+        const auto [tplane, tstride] = target_plane(c);
+        const KeySeg kd{d_items[0].ptr, nd, c->d_src.ptr, c->d_sstride, d_keys[0].ptr, nullptr, d_err.ptr, nullptr};
+        const KeySeg kr{d_items[1].ptr, nr, tplane, tstride, d_keys[1].ptr, nullptr, d_err.ptr, nullptr};
+        if (path == 0) {
+            rc = launch_grid_keys(c, kd, w[0], h[0], kr, w[1], h[1]);
+        } else if (path == 1) {
+            if (nd)
+                launch_bucket_keys(kd.items, nd, h[0], kd.plane, kd.stride, kd.key, nullptr, kd.err, c->stream);
+            if (nr)
+                launch_bucket_keys(kr.items, nr, h[1], kr.plane, kr.stride, kr.key, nullptr, kr.err, c->stream);
+        } else if (path == 2) {
+            launch_bucket_keys_pair(kd, h[0], kr, h[1], c->stream);
+        } else {
+            BlockSums bs, bt;
+            rc = plane_block_sums(c, bs, bt);
+            if (rc == FRAC_OK)
+                launch_bucket_keys_bs(kd, bs, w[0], h[0], kr, bt, w[1], h[1], c->stream);
+        }
+        if (rc == FRAC_OK)
+            e = hipGetLastError();
+        uint32_t err = 0;
+        uint32_t* out[2] = {dom_keys, rng_keys};
+        for (int s = 0; s < 2 && rc == FRAC_OK && e == hipSuccess; ++s)
+            if (cnt[s])
+                e = hipMemcpyAsync(out[s], d_keys[s].ptr, (size_t)cnt[s] * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                   c->stream);
+        if (rc == FRAC_OK && e == hipSuccess)
+            e = hipMemcpyAsync(&err, d_err.ptr, sizeof(err), hipMemcpyDeviceToHost, c->stream);
+        // the call's buffers go when it returns: the stream is idle by then, whatever happened above
+        const hipError_t es = hipStreamSynchronize(c->stream);
+        if (rc != FRAC_OK)
+            return rc;
+        FRAC_HIP(c, e);
+        FRAC_HIP(c, es);
+        if (err)
+            return c->fail(FRAC_E_INVALID, "item category outside -1..5");
+    }
+    return FRAC_OK;
+}
+
+// Test hook: the stable bucket sort (launch_bucket_sorts) of two host key arrays, both sides through the same
+// launches on the current device's null stream.  dn: a device-side count (UINT32_MAX: none).  The orders are
+// filled with 0xffffffff first, so the positions the sort did not write show.
+int frac_debug_bucket_sort(const uint32_t* keys_a, uint32_t na, uint32_t dn_a, const uint32_t* keys_b, uint32_t nb,
+                           uint32_t dn_b, uint32_t* order_a, uint32_t* first_a, uint32_t* order_b, uint32_t* first_b)
+{
+    auto bad = [](const std::string& m, int code) {
+        g_last_error = m;
+        return code;
+    };
+    const uint32_t* in[2] = {keys_a, keys_b};
+    uint32_t* order[2] = {order_a, order_b};
+    uint32_t* first[2] = {first_a, first_b};
+    const uint32_t cnt[2] = {na, nb}, dn[2] = {dn_a, dn_b};
+    for (int s = 0; s < 2; ++s) {
+        if (!first[s] || (cnt[s] && !(in[s] && order[s])))
+            return bad("frac_debug_bucket_sort: NULL array", FRAC_E_INVALID);
+        for (uint32_t i = 0; i < cnt[s]; ++i)
+            if (in[s][i] >= (uint32_t)kMaxBuckets)
+                return bad("frac_debug_bucket_sort: key outside 0..7", FRAC_E_INVALID);
+    }
+    DBuf<uint32_t> d_keys[2], d_out[2], d_cnt, d_first, d_dn;
+    const uint32_t tiles[2] = {std::max<uint32_t>((na + kBkTile - 1) / kBkTile, 1u),
+                               std::max<uint32_t>((nb + kBkTile - 1) / kBkTile, 1u)};
+    hipError_t e = d_cnt.ensure((size_t)(tiles[0] + tiles[1]) * kMaxBuckets);
+    if (e == hipSuccess)
+        e = d_first.ensure(2 * (kMaxBuckets + 1));
+    if (e == hipSuccess)
+        e = d_dn.ensure(2);
+    if (e == hipSuccess)
+        e = hipMemcpy(d_dn.ptr, dn, sizeof(dn), hipMemcpyHostToDevice);
+    for (int s = 0; s < 2 && e == hipSuccess; ++s) {
+        e = d_keys[s].ensure(cnt[s]);
+        if (e == hipSuccess)
+            e = d_out[s].ensure(cnt[s]);
+        if (e == hipSuccess && cnt[s])
+            e = hipMemcpy(d_keys[s].ptr, in[s], (size_t)cnt[s] * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess)
+            e = hipMemset(d_out[s].ptr, 0xff, std::max<size_t>(cnt[s], 1) * sizeof(uint32_t));
+    }
+    if (e == hipSuccess) {
+        const BkSeg sa = bk_seg_of(d_keys[0].ptr, na, dn_a == UINT32_MAX ? nullptr : d_dn.ptr, d_cnt.ptr, d_first.ptr,
+                                   d_out[0].ptr);
+        const BkSeg sb = bk_seg_of(d_keys[1].ptr, nb, dn_b == UINT32_MAX ? nullptr : d_dn.ptr + 1,
+                                   d_cnt.ptr + (size_t)sa.tiles * kMaxBuckets, d_first.ptr + kMaxBuckets + 1,
+                                   d_out[1].ptr);
+        launch_bucket_sorts(sa, sb, nullptr);
+        e = hipGetLastError();
+    }
+    for (int s = 0; s < 2 && e == hipSuccess; ++s) {
+        e = hipMemcpy(first[s], d_first.ptr + s * (kMaxBuckets + 1), (kMaxBuckets + 1) * sizeof(uint32_t),
+                      hipMemcpyDeviceToHost);
+        if (e == hipSuccess && cnt[s])
+            e = hipMemcpy(order[s], d_out[s].ptr, (size_t)cnt[s] * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    }
+    if (e != hipSuccess) {
+        (void)hipDeviceSynchronize(); // nothing may still run on the buffers that go with this call
+        return bad(std::string("frac_debug_bucket_sort: ") + hipGetErrorString(e), FRAC_E_DEVICE);
+    }
+    return FRAC_OK;
+}
+
 frac_ctx* frac_create(int device, const frac_params* params)
 {
     std::string msg;

@@ -39,6 +39,21 @@ static int plane_block_sums(frac_ctx* c, BlockSums& bs, BlockSums& bt)
     return FRAC_OK;
 }
 
+// Both grids' keys (domains dw × dh, ranges rw × rh): from the planes' block sums when every side is at
+// most 32, else by the row kernels
+static int launch_grid_keys(frac_ctx* c, const KeySeg& kd, uint32_t dw, uint32_t dh, const KeySeg& kr, uint32_t rw,
+                            uint32_t rh)
+{
+    if (dh <= 32 && dw <= 32 && rh <= 32 && rw <= 32) {
+        BlockSums bs, bt;
+        FRAC_TRY(plane_block_sums(c, bs, bt));
+        launch_bucket_keys_bs(kd, bs, dw, dh, kr, bt, rw, rh, c->stream);
+    } else {
+        launch_bucket_keys_pair(kd, dh, kr, rh, c->stream);
+    }
+    return FRAC_OK;
+}
+
 // The classifier buckets on the device (fracenc_bucket.hip): d_porig (pool position → domain index),
 // d_rord (ranges in bucket order), d_rkey (per range bucket); first[b] / rfirst[b] = the first pool
 // position / bucket-sorted range of bucket b (b = 0..kMaxBuckets).  One small synchronous copy.
@@ -73,13 +88,7 @@ int device_buckets(frac_ctx* c, int nb, uint32_t* dfirst, uint32_t* rfirst)
     // both grids' keys, in one launch for the usual 2n → n geometry
     const KeySeg kd{c->d_doms.ptr, nd, c->d_src.ptr, c->d_sstride, c->d_bk_keys.ptr, nullptr, err, nullptr};
     const KeySeg kr{c->d_ranges.ptr, nr, tplane, tstride, c->d_rkey.ptr, nullptr, err, nullptr};
-    if (c->Sh <= 32 && c->Sw <= 32 && c->nh <= 32 && c->nw <= 32) { // from the planes' block sums
-        BlockSums bs, bt;
-        FRAC_TRY(plane_block_sums(c, bs, bt));
-        launch_bucket_keys_bs(kd, bs, c->Sw, c->Sh, kr, bt, c->nw, c->nh, c->stream);
-    } else {
-        launch_bucket_keys_pair(kd, c->Sh, kr, c->nh, c->stream);
-    }
+    FRAC_TRY(launch_grid_keys(c, kd, c->Sw, c->Sh, kr, c->nw, c->nh));
     const BkSeg sd = bk_seg_of(c->d_bk_keys.ptr, nd, nullptr, c->d_bk_cnt.ptr, first, c->d_porig.ptr);
     const BkSeg sr = bk_seg_of(c->d_rkey.ptr, nr, nullptr, c->d_bk_cnt.ptr + (size_t)sd.tiles * kMaxBuckets,
                                first + kMaxBuckets + 1, c->d_rord.ptr);

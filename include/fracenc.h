@@ -513,6 +513,25 @@ uint32_t frac_debug_sort_chunk(void);
 int frac_debug_sort_pairs(const uint32_t* keys, const uint32_t* vals, uint32_t n, const uint32_t* keys_b,
                           const uint32_t* vals_b, uint32_t n_b, uint32_t bits, uint32_t* out_keys,
                           uint32_t* out_vals, uint32_t* out_keys_b, uint32_t* out_vals_b);
+/* frac_debug_bucket_keys computes the classifier bucket keys (category + 1; a stored category other than -1 is
+ * passed through) of nd domains on the context's source plane and nr ranges on its target plane, as a classified
+ * run does before it sorts its pool (csrc/fracenc_bucket.hip).  path: 0 the run's own choice of kernels, 1 the
+ * row kernels grid by grid (one wave per item above 64 rows), 2 the paired launch, 3 the planes' block sums.
+ * FRAC_E_INVALID, before any launch: no frame set, an item outside its plane, a category outside -1..5, or, where
+ * the row kernels run, a grid of more than one item size.  It changes nothing another call reads.
+ * frac_debug_bucket_sort runs the stable bucket sort on two host key arrays (keys 0..7, either side may be
+ * empty), both through the same launches: dn_* is a count the kernels read from device memory (only the first
+ * min(dn, n) keys are sorted) or UINT32_MAX for none; order_* [n] is filled with 0xffffffff before the sort and
+ * receives the sorted indices, first_* [9] the first sorted position of each key and the count.
+ * frac_debug_bucket_tile is the sort's items per workgroup, frac_debug_bucket_self_tiles the most tiles of a
+ * sort that runs without the separate scan launch. */
+uint32_t frac_debug_bucket_tile(void);
+uint32_t frac_debug_bucket_self_tiles(void);
+int frac_debug_bucket_keys(frac_ctx* ctx, const frac_grid_item* doms, uint32_t nd, const frac_grid_item* rngs,
+                           uint32_t nr, int path, uint32_t* dom_keys, uint32_t* rng_keys);
+int frac_debug_bucket_sort(const uint32_t* keys_a, uint32_t na, uint32_t dn_a, const uint32_t* keys_b, uint32_t nb,
+                           uint32_t dn_b, uint32_t* order_a, uint32_t* first_a, uint32_t* order_b,
+                           uint32_t* first_b);
 
 #ifdef __cplusplus
 }

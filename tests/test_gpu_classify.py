@@ -131,3 +131,48 @@ def test_classifier_pool_beyond_the_one_pass_sort(oracle):
          "t": got["transform"], "dist": got["distance"], "s": got["contrast"], "o": got["brightness"]}
     for k in FIELDS:
         np.testing.assert_array_equal(g[k], want[k], err_msg=k)
+
+
+# Classified searches whose items reach the key kernels for large items (fracenc_bucket.hip): stored categories
+# −1, so the device classifies.  (plane, domain size, domain offset, range size): the domain grid is cut so that
+# no rotation of a rectangular domain samples outside the plane.
+LARGE_ITEM_SEARCHES = {
+    # keys_rows_item<64> for the domains, whose 16-wide quadrants wrap the reference's uint16_t; <32> for the ranges
+    "32x64_over_16x32": ("noise5_160x192", (32, 64), (8, 16), (16, 32)),
+    # bucket_keys (one wave per item, above 64 rows) for the domains, keys_rows_item<64> for the ranges
+    "128_over_64": ("value71_256x192", (128, 128), (16, 16), (64, 64)),
+    # the paired launch bucket_keys_rows2<16, 8>
+    "64x16_over_32x8": ("noise72_160x96", (64, 16), (8, 4), (32, 8)),
+}
+
+
+@pytest.mark.parametrize("engine", [F.ENGINE_VALU, F.ENGINE_MFMA, F.ENGINE_SEA])
+@pytest.mark.parametrize("name", list(LARGE_ITEM_SEARCHES))
+def test_classified_search_with_large_items(oracle, name, engine):
+    import classifier_ref as R
+
+    pl, ds, doff, rs = LARGE_ITEM_SEARCHES[name]
+    p = R.plane(pl)
+    H, W = p.shape
+    M = max(ds)
+    doms = F.create_uniform_grid(W - (M - ds[0]), H - (M - ds[1]), ds, doff)
+    rngs = F.create_uniform_grid(W, H, rs, rs)
+    assert len(doms) > 40 and len(rngs) >= 12 and (doms["category"] == -1).all() and (rngs["category"] == -1).all()
+    cd, cr = F.preclassify(p, doms), F.preclassify(p, rngs)
+    np.testing.assert_array_equal(cd["category"], R.categories(p, doms))
+    np.testing.assert_array_equal(cr["category"], R.categories(p, rngs))
+    want, rej, _ = oracle.estimate(p, cd, cr, T=4, use_classifier=True)
+    assert (want["dw"] != 0).sum() * 2 > len(rngs)  # most ranges have a domain of their category
+    got = {}
+    for label, (d, r) in (("device", (doms, rngs)), ("host", (cd, cr))):
+        with F.Engine(0, 4, True, 0.0, -1.0, engine) as e:
+            e.set_frame(p)
+            e.set_domains(d)
+            out, st = e.search(r)
+        got[label] = out
+        g = {"x": out["x"], "y": out["y"], "dx": out["dx"], "dy": out["dy"], "dw": out["sw"], "dh": out["sh"],
+             "t": out["transform"], "dist": out["distance"], "s": out["contrast"], "o": out["brightness"]}
+        for k in FIELDS:
+            np.testing.assert_array_equal(g[k], want[k], err_msg=f"{label}-classified: {k}")
+        assert st["rejected_mappings"] == rej, label
+    assert got["device"].tobytes() == got["host"].tobytes()

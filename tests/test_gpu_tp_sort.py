@@ -4,7 +4,8 @@ sides.  Sizes around the chunk (C items per workgroup: 0, 1, a wave's 63 / 64, C
 side paired with a different size of the list and one side empty; 16-, 17- and 19-bit keys (two and three
 passes); key patterns that leave one digit or both constant, reverse the input, tie in long runs across chunk
 boundaries, and — with bucket bits — are non-monotone in the input as the ranges' buckets are.  Every case runs
-twice: the second output must be byte-identical."""
+twice: the second output must be byte-identical.  Sizes of 64 chunks, one item more and 65 C + 17 run the scan of
+the per-chunk counts (tp_sort_offsets) through its carry from one 64-chunk round to the next."""
 import numpy as np
 import pytest
 
@@ -64,6 +65,18 @@ def test_sort_is_the_stable_order(n, nb, bits, pattern):
         np.testing.assert_array_equal(got[1], wv, err_msg=f"side {side}: values")
     for x, y in zip(first, again):
         assert x.tobytes() == y.tobytes(), "two runs on the same input differ"
+
+
+# 64 chunks (one round of tp_sort_offsets' scan, every lane live), 65 (a second round of one lane) and 66
+LONG = [64 * C, 64 * C + 1, 65 * C + 17]
+LONG_PAIRS = [(LONG[0], LONG[2]), (LONG[1], 0), (LONG[2], LONG[1]), (C + 1, LONG[0])]
+
+
+@pytest.mark.parametrize("pattern", ["few_values", "buckets"])
+@pytest.mark.parametrize("bits", [16, 19])
+@pytest.mark.parametrize("n,nb", LONG_PAIRS, ids=[f"{a}+{b}" for a, b in LONG_PAIRS])
+def test_more_chunks_than_a_wave_scans_at_once(n, nb, bits, pattern):
+    test_sort_is_the_stable_order(n, nb, bits, pattern)
 
 
 def test_high_key_bits_are_carried_not_sorted():

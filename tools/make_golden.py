@@ -316,6 +316,28 @@ def main():
                                                            "grid": [512, 512, 4, 4, 4, 2]}).encode(), dtype=np.uint8))
         print(f"  opencl_classify: {len(items)} items, categories {np.bincount(items['category'] + 1)}")
 
+    # -- the reference's preclassify on rectangles: tall items whose quadrants are at most 16 wide wrap
+    # ImageStatistics2::sum's uint16_t (ImageStatistics.hpp:13-17), 34×64 (quadrants 17 wide) does not, 30×70 has
+    # odd halves.  The grids are laid out here (item by item while they fit, as tests/classifier_ref.py:grid):
+    # createUniformGrid asserts on a plane that is no multiple of the item size.
+    if want("opencl_classify_rect"):
+        pl = np.random.default_rng(5).integers(0, 256, (192, 160), dtype=np.uint8)
+        H, W = pl.shape
+        grids = [((32, 64), (16, 32)), ((32, 128), (8, 16)), ((16, 128), (8, 16)), ((34, 64), (16, 32)),
+                 ((30, 70), (7, 9))]
+        rows = [(x, y, w, h, -1) for (w, h), (ox, oy) in grids for y in range(0, H - h + 1, oy)
+                for x in range(0, W - w + 1, ox)]
+        items = np.array(rows, dtype=ITEM)
+        lib.fr_classify_items.restype = C.c_int
+        lib.fr_classify_items.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]
+        lib.fr_classify_items(pl.ctypes.data, W, H, W, items.ctypes.data, len(items))
+        np.savez_compressed(os.path.join(GOLD, "opencl_classify_rect.npz"), items=items,
+                            meta=np.frombuffer(json.dumps({
+                                "plane": "np.random.default_rng(5).integers(0, 256, (192, 160), dtype=np.uint8)",
+                                "plane_sha256": sha256(pl),
+                                "grids": [[w, h, ox, oy] for (w, h), (ox, oy) in grids]}).encode(), dtype=np.uint8))
+        print(f"  opencl_classify_rect: {len(items)} items, categories {np.bincount(items['category'] + 1)}")
+
     # -- S1 4096^2 strided sample (C3 parity on a sample) ----------------------
     if want("s1_4096_sample"):
         t0 = time.time()
