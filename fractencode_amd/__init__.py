@@ -237,6 +237,12 @@ def lib() -> C.CDLL:
                                            C.POINTER(FracStats)]),
             "frac_encode_quadtree_leaves": (i32, [vp, C.POINTER(FracQuadtreeParams), vp, sz, C.POINTER(sz),
                                                   C.POINTER(FracStats)]),
+            "frac_quadtree_rate_build": (i32, [vp, u32, u32, C.POINTER(FracStats)]),
+            "frac_quadtree_rate_sizes": (i32, [vp, u32, u32, vp, sz, vp, vp, vp]),
+            "frac_quadtree_rate_fit": (i32, [vp, u32, u32, C.c_uint64, C.POINTER(C.c_double),
+                                             C.POINTER(C.c_uint64), C.POINTER(u32)]),
+            "frac_quadtree_rate_leaves": (i32, [vp, C.c_double, vp, sz, C.POINTER(sz)]),
+            "frac_frq1_size": (i32, [u32, u32, u32, u32, u32, u32, u32, C.POINTER(u32), C.POINTER(C.c_uint64)]),
             "frac_rgb_to_yuv_device": (i32, [vp, vp, u32, u32, u32, vp, u32, vp, u32, vp, u32]),
             "frac_rgb_to_yuv": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]),
             "frac_yuv_to_rgb_device": (i32, [vp, vp, u32, u32, u32, vp, u32, vp, u32, vp, u32]),
@@ -415,6 +421,19 @@ def pack_frq1(leaves: np.ndarray, width: int, height: int, max_size: int, min_si
     if lib().frac_pack_frq1(*args, buf.ctypes.data_as(C.c_void_p), n.value, C.byref(n)) != 0:
         raise FracError(last_error())
     return buf.tobytes()
+
+
+def frq1_size(width: int, height: int, max_size: int, min_size: int, splits, transforms: int = 4,
+              contrast_bits: int = 5, brightness_bits: int = 7) -> int:
+    """The size in bytes of the FRQ1 stream of a partition of a width×height frame that splits splits[k] nodes
+    of level k (sides max_size >> k; one count per level but the last), on the host (frac_frq1_size): the header,
+    per level a bitmap over its nodes (all but the last) and its leaves' records, each padded to a dword."""
+    s = (C.c_uint32 * 3)(*([int(v) for v in splits] + [0, 0, 0])[:3])
+    n = C.c_uint64(0)
+    if lib().frac_frq1_size(width, height, max_size, min_size, transforms, contrast_bits, brightness_bits, s,
+                            C.byref(n)) != 0:
+        raise FracError(last_error())
+    return n.value
 
 
 def frc3_info(stream) -> dict:
@@ -757,6 +776,67 @@ class Engine:
         d = st.as_dict()
         d["items"] = n.value
         return (buf[: min(n.value, cap)] if out is not None else buf[: n.value].copy()), d
+
+    def quadtree_rate(self, max_size: int = 16, min_size: int = 4) -> dict:
+        """Search the full quadtree of the frame set on this engine once (frac_quadtree_rate_build): every node
+        of every level, whatever a split distance would reach.  Afterwards rate_sizes, rate_fit and rate_leaves
+        answer for any split distance without a search, until the next setter, run() or encode_quadtree().
+        Returns the summed stats dict."""
+        st = FracStats()
+        self._check(lib().frac_quadtree_rate_build(self._ctx, max_size, min_size, C.byref(st)))
+        self._rate_sizes = (max_size, min_size)
+        return st.as_dict()
+
+    def rate_sizes(self, splits, contrast_bits: int = 5, brightness_bits: int = 7):
+        """Per split distance in `splits` (any doubles) what encode_quadtree_stream would return there:
+        (bytes uint64 [n], leaves uint32 [n], per-level split counts uint32 [n, 4])."""
+        t = np.ascontiguousarray(splits, dtype=np.float64).reshape(-1)
+        n = len(t)
+        size, leaves, s = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros((n, 4), np.uint32)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if n else None  # noqa: E731
+        self._check(lib().frac_quadtree_rate_sizes(self._ctx, contrast_bits, brightness_bits, ptr(t), n, ptr(size),
+                                                   ptr(leaves), ptr(s)))
+        return size, leaves, s
+
+    def rate_fit(self, max_bytes: int, contrast_bits: int = 5, brightness_bits: int = 7):
+        """The smallest split distance whose FRQ1 stream has at most max_bytes (exact: the minimum over every
+        candidate of the full tree) → (split distance, bytes, leaves).  FracError when nothing fits."""
+        t, size, leaves = C.c_double(0.0), C.c_uint64(0), C.c_uint32(0)
+        self._check(lib().frac_quadtree_rate_fit(self._ctx, contrast_bits, brightness_bits, max_bytes, C.byref(t),
+                                                 C.byref(size), C.byref(leaves)))
+        return t.value, size.value, leaves.value
+
+    def rate_leaves(self, split: float, out=None, allow_short: bool = False) -> np.ndarray:
+        """The QT_LEAF leaves of the partition at `split`, as encode_quadtree(leaves=True) returns them, from the
+        rate state (no search).  `out`: a contiguous QT_LEAF array (e.g. pinned host memory, which the device
+        writes directly) of at least (W/min_size)·(H/min_size) items, or shorter with allow_short (the leaves
+        past it are counted but not written); a view of it is returned."""
+        W, H = self._frame_wh
+        m = getattr(self, "_rate_sizes", (0, 0))[1]  # no build yet: the library refuses the call
+        cap = max((W // m) * (H // m), 1) if m else 1
+        if out is not None:
+            if out.dtype != QT_LEAF or not out.flags.c_contiguous or (len(out) < cap and not allow_short):
+                raise ValueError(f"out must be a contiguous QT_LEAF array of at least {cap} items")
+            buf, cap = out, len(out)
+        else:
+            buf = np.empty(cap, dtype=QT_LEAF)
+        n = C.c_size_t(0)
+        self._check(lib().frac_quadtree_rate_leaves(self._ctx, split, buf.ctypes.data, cap, C.byref(n)))
+        return buf[: min(n.value, cap)]
+
+    def encode_quadtree_to_size(self, max_bytes: int, max_size: int = 16, min_size: int = 4,
+                                contrast_bits: int = 5, brightness_bits: int = 7):
+        """The best quadtree partition of the frame set on this engine whose FRQ1 stream has at most max_bytes:
+        quadtree_rate + rate_fit + rate_leaves + pack_frq1.  Returns (bytes, info): info has the stats of the
+        full-tree search plus split_distance (the smallest that fits), bytes and items."""
+        info = self.quadtree_rate(max_size, min_size)
+        t, size, n = self.rate_fit(max_bytes, contrast_bits, brightness_bits)
+        leaves = self.rate_leaves(t)
+        W, H = self._frame_wh
+        stream = pack_frq1(leaves, W, H, max_size, min_size, self._p.transforms, bool(self._p.use_classifier),
+                           contrast_bits, brightness_bits)
+        info.update(split_distance=t, bytes=size, items=n)
+        return stream, info
 
     def classify(self, items: np.ndarray, target_plane: bool = False) -> np.ndarray:
         """BrightnessBlocksClassifier2 categories of `items` computed on the device plane set by

@@ -6,6 +6,7 @@
 //   fracenc_launch.hip   variant selection, the engines' launch paths, the fp32 fallback
 //   fracenc_quadtree.hip quadtree frames, host- and device-planned
 //   fracenc_codec.hip    decode, FRC1 and FRQ1 pack / parse / decode, colour conversion
+//   fracenc_qtrate.hip   quadtree rate sweep: the full tree searched once, sizes, fit and leaves per threshold
 //
 // Host logic mirrored from the reference:
 //   classifier gating      encode/Classifier2.cpp:8-81   (categories computed on the host,
@@ -46,6 +47,7 @@ using namespace fracenc;
 #include "fracenc_launch.hip"
 #include "fracenc_quadtree.hip"
 #include "fracenc_codec.hip"
+#include "fracenc_qtrate.hip"
 
 namespace {
 
@@ -414,6 +416,7 @@ static void results_gone(frac_ctx* c)
 {
     c->ran = false;
     c->fb_pending = false;
+    c->rate.ready = false;
 }
 
 int frac_set_params(frac_ctx* c, const frac_params* params)
@@ -457,6 +460,7 @@ static void planes_changed(frac_ctx* c, uint32_t sw, uint32_t sh, uint32_t tw, u
     c->same_plane = same;
     c->planes_set = true;
     c->ran = false;
+    c->rate.ready = false;
 }
 
 int frac_set_planes(frac_ctx* c, const uint8_t* src, uint32_t sw, uint32_t sh, uint32_t sstride, const uint8_t* tgt,
@@ -592,6 +596,7 @@ int frac_run(frac_ctx* c)
     }
     // a new run owns the records: the previous run's fused-resolver state and its unsettled fallback
     // (whose saved args may name buffers prepare() is about to reallocate) go, whichever path runs next
+    c->rate.ready = false; // a rate state describes the frame as it was searched before this run
     c->fit_fused = false;
     c->fb_pending = false;
     if (c->dirty)

@@ -279,6 +279,35 @@ struct frac_ctx {
     DBuf<uint8_t> d_qt_tmp;
     size_t qt_tmp_bytes = 0;
     bool qt_dvalid[5] = {false, false, false, false, false};
+    // quadtree rate sweep (fracenc_qtrate.hip): the full tree of the last frac_quadtree_rate_build, level-major
+    // (level k's N_k = 4^k·N_0 nodes from off[k]), and what answers every threshold from it.  Everything is
+    // sized at build time, for the worst case; the readers allocate nothing from a device count.
+    struct QtRate {
+        bool ready = false;                // a readable state: cleared by every setter, frac_run and the quadtree calls
+        uint32_t W = 0, H = 0, max_size = 0, min_size = 0, levels = 0, transforms = 0;
+        uint32_t nodes[4] = {0, 0, 0, 0};  // N_k of the full tree
+        uint32_t off[5] = {0, 0, 0, 0, 0}; // first node of level k; off[levels] = the tree's node count
+        uint32_t ndoms[4] = {0, 0, 0, 0};  // domains of level k: createUniformGrid(W, H, 2n, n)
+        uint32_t nkeys = 0;                // nodes that can split: off[levels − 1]
+        DBuf<frac_qt_leaf> d_nodes;        // every node's record, packed as qt_leaf_of
+        DBuf<double> d_e;                  // [nkeys] split keys e(v) = min(d(v), e(parent(v)))
+        DBuf<unsigned long long> d_key, d_skey; // their order-preserving bit patterns, unsorted / sorted
+        DBuf<uint32_t> d_lvl, d_slvl;      // the keys' levels, unsorted / sorted with them
+        DBuf<uint32_t> d_pre;              // [3][nkeys + 1] per level: keys of that level before sorted position i
+        DBuf<uint32_t> d_flag, d_rank;     // [nodes + 1] frac_quadtree_rate_leaves: leaf flags, their exclusive scan
+        DBuf<uint8_t> d_tmp;               // hipcub's scratch, the largest of the sort and the two scans
+        size_t tmp_bytes = 0;
+        DBuf<double> d_split;              // frac_quadtree_rate_sizes: thresholds in, results out
+        DBuf<unsigned long long> d_bytes;
+        DBuf<uint32_t> d_counts;           // [n][5]: leaves, splits[4]
+        DBuf<unsigned long long> d_fit;    // frac_quadtree_rate_fit: {least fitting key, least size}
+        DBuf<frac_qt_leaf> d_out;          // frac_quadtree_rate_leaves into pageable memory: staged here
+        struct Result {
+            unsigned long long key, bytes, min_bytes;
+            uint32_t leaves, found;
+        };
+        Pinned<Result> h_res;              // mapped: the fit's answer, the emit's leaf count
+    } rate;
     DBuf<uint8_t> d_sea_tmp;
     DBuf<unsigned long long> d_sea_count; // candidates the SEA search evaluated
     DBuf<unsigned long long> d_tp_evals;  // tiled form: per group, the (range, domain) pairs of its window

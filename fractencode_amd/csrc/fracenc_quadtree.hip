@@ -40,6 +40,54 @@ struct LevelGrid {
     }
 };
 
+// the cached level grids belong to one frame size: another size starts them afresh
+void qt_grids_for(frac_ctx* c, uint32_t W, uint32_t H)
+{
+    if (c->qt_w == W && c->qt_h == H)
+        return;
+    for (auto& g : c->qt_doms)
+        g.clear();
+    for (auto& v : c->qt_dvalid)
+        v = false;
+    c->qt_w = W;
+    c->qt_h = H;
+}
+
+// A host-planned level's statistics (after its frac_run, before level.out()): the counters accumulate on the
+// device in d_qt_stats (no per-level download or host loop), the rest is the host's
+void qt_host_level_stats(frac_ctx* c, uint32_t nr, frac_stats& total)
+{
+    QtBuckets qb{};
+    qb.nb = (uint32_t)c->bucket_begin.size();
+    for (uint32_t b = 0; b < qb.nb && b < (uint32_t)kMaxBuckets; ++b) {
+        qb.beg[b] = c->bucket_begin[b];
+        qb.end[b] = c->bucket_end[b];
+    }
+    const bool sea_ran = c->engine_ran == FRAC_ENGINE_SEA && c->form_ran == FRAC_FORM_SEA;
+    qt_level_stats<<<(nr + 255) / 256, 256, 0, c->stream>>>(
+        c->d_aux.ptr, c->d_rkey.ptr, c->d_porig.ptr, nr, (uint64_t)c->doms.size(), c->p.use_classifier ? 1 : 0, qb,
+        sea_ran ? c->d_sea_count.ptr : nullptr, c->d_qt_stats.ptr);
+    total.total_mappings += (uint64_t)c->doms.size() * nr;
+    total.engine = c->engine_ran;
+    total.search_form = c->form_ran;
+    total.matrix_flops += c->flops_ran;
+    if (!sea_ran)
+        total.evaluated_mappings += c->evaluated_ran;
+}
+
+// the host-planned levels' counters, read once after the last level
+int qt_host_read_stats(frac_ctx* c, frac_stats& total)
+{
+    unsigned long long acc[5] = {0ull, 0ull, 0ull, 0ull, 0ull};
+    FRAC_HIP(c, hipMemcpy(acc, c->d_qt_stats.ptr, sizeof(acc), hipMemcpyDeviceToHost));
+    total.rejected_mappings = acc[0];
+    total.hit_ranges = acc[1];
+    total.fallback_ranges = acc[2];
+    total.empty_ranges = acc[3];
+    total.evaluated_mappings += acc[4];
+    return FRAC_OK;
+}
+
 // Whether a quadtree frame runs device-planned (qt_encode_dev): the MFMA engine at every level (AUTO
 // or MFMA requested; the VALU and SEA engines keep the host-planned levels below), and no level in
 // the all-fallback regime (a threshold that can be met in the inexact regime).
@@ -395,6 +443,7 @@ static int encode_quadtree_impl(frac_ctx* c, const frac_quadtree_params* qp, fra
 {
     if (!c)
         return FRAC_E_INVALID;
+    c->rate.ready = false; // the levels reuse the run's buffers: a rate state (fracenc_qtrate.hip) ends here
     // the levels' runs write no tuples into a frac_run sink (it is sized for the context's own ranges)
     struct SinkAside {
         frac_ctx* c;
@@ -426,15 +475,8 @@ static int encode_quadtree_impl(frac_ctx* c, const frac_quadtree_params* qp, fra
     };
     frac_stats total{};
     HostTrace tr("quadtree");
-    if (c->qt_w != W || c->qt_h != H) {
-        for (auto& g : c->qt_doms)
-            g.clear();
-        for (auto& v : c->qt_dvalid)
-            v = false;
-        c->qt_w = W;
-        c->qt_h = H;
-    }
-    if (out32 && !qt_device_planned(c, qp)) {
+    qt_grids_for(c, W, H);
+    if (out32 &&!qt_device_planned(c, qp)) {
         // the host-planned levels (other engines, tuning knobs): the records, then packed here
         std::vector<frac_encode_item> rec(cap);
         FRAC_TRY(encode_quadtree_impl(c, qp, cap ? rec.data() : nullptr, nullptr, cap, n_out, stats));
@@ -480,24 +522,8 @@ static int encode_quadtree_impl(frac_ctx* c, const frac_quadtree_params* qp, fra
         // the level's statistics accumulate on the device (no per-level download or host loop); the
         // counters are read once after the last level, the event times after this level's count
         const uint32_t nr = (uint32_t)level_nr;
-        if (stats) {
-            QtBuckets qb{};
-            qb.nb = (uint32_t)c->bucket_begin.size();
-            for (uint32_t b = 0; b < qb.nb && b < (uint32_t)kMaxBuckets; ++b) {
-                qb.beg[b] = c->bucket_begin[b];
-                qb.end[b] = c->bucket_end[b];
-            }
-            const bool sea_ran = c->engine_ran == FRAC_ENGINE_SEA && c->form_ran == FRAC_FORM_SEA;
-            qt_level_stats<<<(nr + 255) / 256, 256, 0, c->stream>>>(
-                c->d_aux.ptr, c->d_rkey.ptr, c->d_porig.ptr, nr, (uint64_t)c->doms.size(), c->p.use_classifier ? 1 : 0,
-                qb, sea_ran ? c->d_sea_count.ptr : nullptr, c->d_qt_stats.ptr);
-            total.total_mappings += (uint64_t)c->doms.size() * nr;
-            total.engine = c->engine_ran;
-            total.search_form = c->form_ran;
-            total.matrix_flops += c->flops_ran;
-            if (!sea_ran)
-                total.evaluated_mappings += c->evaluated_ran;
-        }
+        if (stats)
+            qt_host_level_stats(c, nr, total);
         level.out();
         tr.mark("level stats (enqueue)");
         FRAC_HIP(c, c->d_qt_flags.ensure(nr));
@@ -545,13 +571,7 @@ static int encode_quadtree_impl(frac_ctx* c, const frac_quadtree_params* qp, fra
                               hipMemcpyDeviceToHost));
     tr.mark("leaves D2H");
     if (stats) {
-        unsigned long long acc[5] = {0ull, 0ull, 0ull, 0ull, 0ull};
-        FRAC_HIP(c, hipMemcpy(acc, c->d_qt_stats.ptr, sizeof(acc), hipMemcpyDeviceToHost));
-        total.rejected_mappings = acc[0];
-        total.hit_ranges = acc[1];
-        total.fallback_ranges = acc[2];
-        total.empty_ranges = acc[3];
-        total.evaluated_mappings += acc[4];
+        FRAC_TRY(qt_host_read_stats(c, total));
         *stats = total;
     }
     return FRAC_OK;

@@ -156,13 +156,19 @@ const char* frac_last_error(const frac_ctx* ctx);
  * planes changed between runs.  The results of a run are readable from that frac_run until the next call of
  * a setter — frac_set_params, frac_set_domains, frac_set_ranges, frac_set_frame, frac_set_planes,
  * frac_set_frame_device, frac_set_frame_device_async, frac_set_frame_async — or of frac_encode_quadtree /
- * frac_encode_quadtree_leaves (which search lists of their own).  From such a call to the next frac_run every
- * reader — frac_fetch, frac_fetch_tuples, frac_copy_tuples_device, frac_copy_results_device, frac_pack_frc1,
- * frac_decode_results — returns FRAC_E_STATE, and frac_device_results returns NULL: the old winners are never
- * paired with the new parameters, domain list, ranges or planes.  A setter that fails its own argument checks
- * changes nothing.  frac_set_stream, frac_set_tuple_sink, frac_sync, frac_classify_items, frac_decode,
+ * frac_encode_quadtree_leaves / frac_quadtree_rate_build (which search lists of their own).  From such a call to
+ * the next frac_run every reader — frac_fetch, frac_fetch_tuples, frac_copy_tuples_device,
+ * frac_copy_results_device, frac_pack_frc1, frac_decode_results — returns FRAC_E_STATE, and
+ * frac_device_results returns NULL: the old winners are never paired with the new parameters, domain list,
+ * ranges or planes.  A setter that fails its own argument checks changes nothing.  frac_set_stream,
+ * frac_set_tuple_sink, frac_sync, frac_classify_items, frac_decode,
  * frac_decode_frc1, frac_decode_frq1, frac_decode_frc3, frac_decode_frc3_device and the colour conversions
- * (frac_rgb_to_yuv, frac_rgb_to_yuv_device, frac_yuv_to_rgb, frac_yuv_to_rgb_device) leave the results readable. */
+ * (frac_rgb_to_yuv, frac_rgb_to_yuv_device, frac_yuv_to_rgb, frac_yuv_to_rgb_device) leave the results readable.
+ * The rate state of frac_quadtree_rate_build has the same life, from that call: it is readable
+ * (frac_quadtree_rate_sizes, frac_quadtree_rate_fit, frac_quadtree_rate_leaves) until the next setter above,
+ * frac_run, frac_encode_quadtree / frac_encode_quadtree_leaves or frac_quadtree_rate_build, after which its
+ * readers return FRAC_E_STATE; the calls that leave a run's results readable leave it readable too, and so do
+ * its own readers. */
 int frac_set_params(frac_ctx* ctx, const frac_params* params);
 
 /* Planes are uint8, row-major with the given stride (bytes). Copied to the device.
@@ -434,6 +440,52 @@ int frac_pack_frq1(const frac_qt_leaf* leaves, size_t n, uint32_t width, uint32_
  * 2^24 or more domains are refused (as frac_qt_leaf cannot name them). */
 int frac_decode_frq1(frac_ctx* ctx, const uint8_t* stream, size_t len, uint32_t scale, int max_iter,
                      double rms_eps, uint8_t* plane, size_t plane_bytes, int* iterations, double* rms);
+
+/* ---- quadtree rate sweep: every split distance's FRQ1 size from one search ----
+ * These five symbols were added after ABI 9 without changing FRAC_ABI_VERSION: probe for them by name
+ * (dlsym) when the library may be older.
+ *
+ * The partition frac_encode_quadtree makes at ANY split distance is a function of the distances of the full
+ * tree: level 0 is createUniformGrid(W, H, max_size, max_size) in row-major order, level k + 1 holds, for each
+ * node of level k in order, its quadrants top-left, top-right, bottom-left, bottom-right (N_k = 4^k · N_0), and
+ * the nodes a split distance reaches are a sub-sequence of it in FRQ1's canonical order.  With d(v) the distance
+ * of node v's record (the search frac_encode_quadtree runs for that node at that level) and the split key
+ * e(v) = min(d(v), e(parent(v))) (e = d at level 0), node v of a level above min_size is reached and split
+ * under split distance t exactly when e(v) > t — the comparison frac_encode_quadtree makes, in double.  So
+ * S_k(t) = #{v of level k : e(v) > t} gives the node counts N_{k+1}(t) = 4 · S_k(t), the leaf counts
+ * M_k = N_k(t) − S_k(t) and the stream's size (frac_frq1_size).  The candidates are {0.0} ∪ {e(v)}: between two
+ * neighbouring candidates nothing changes.
+ *
+ * frac_quadtree_rate_build searches the full tree of the frame set on ctx once, level by level on the device
+ * (any engine; arguments, frame limits and statistics as frac_encode_quadtree_leaves'), and keeps every node's
+ * leaf and the sorted keys in the context.  Like frac_encode_quadtree it ends the last run's results and consumes
+ * the range list.  The rate state stays readable until the next setter (see "When results are readable"),
+ * frac_run, frac_encode_quadtree / frac_encode_quadtree_leaves or frac_quadtree_rate_build; without one the three
+ * readers below return FRAC_E_STATE.  The readers search nothing, leave the state and each other's answers
+ * alone and ignore the tuple sink.  A frame without level-0 ranges builds an empty state: 64 bytes, no leaves,
+ * fit 0.0.
+ *  - _sizes: for n thresholds (any doubles: negative, +inf) the stream's bytes with these quantizer widths
+ *    (each in [2, 16]), its leaf count (leaves, may be NULL) and the per-level split counts S_k (splits [n][4],
+ *    may be NULL; 0 from the last level on).
+ *  - _fit: the least candidate whose stream has at most max_bytes — the exact smallest split distance that fits,
+ *    the minimum over the fitting candidates whether or not the size is monotone — with its size and leaf count
+ *    (each pointer may be NULL).  FRAC_E_INVALID when no candidate fits; the message names the smallest size.
+ *  - _leaves: the partition at split distance `split` exactly as frac_encode_quadtree_leaves returns it (order,
+ *    every field), without a search.  *n_out = the leaf count; writes min(count, cap) leaves (out may be NULL to
+ *    query the count).  out: host memory, or device memory, or pinned host memory the device writes directly. */
+int frac_quadtree_rate_build(frac_ctx* ctx, uint32_t max_size, uint32_t min_size, frac_stats* stats);
+int frac_quadtree_rate_sizes(frac_ctx* ctx, uint32_t contrast_bits, uint32_t brightness_bits, const double* split,
+                             size_t n, uint64_t* bytes, uint32_t* leaves, uint32_t* splits);
+int frac_quadtree_rate_fit(frac_ctx* ctx, uint32_t contrast_bits, uint32_t brightness_bits, uint64_t max_bytes,
+                           double* split, uint64_t* bytes, uint32_t* leaves);
+int frac_quadtree_rate_leaves(frac_ctx* ctx, double split, frac_qt_leaf* out, size_t cap, size_t* n_out);
+/* Host only, no ctx (message via frac_last_error(NULL)): the size of the FRQ1 stream of a partition of a
+ * width×height frame that splits splits[k] nodes of level k (k < levels − 1; later entries are not read, splits
+ * may be NULL for a single level): 64 + Σ_k [k < levels − 1: 4·ceil(N_k/32)] + 4·ceil(M_k·record_bits_k/32).
+ * FRAC_E_INVALID for sizes, sides, transforms or bits as frac_pack_frq1 refuses them, and for a splits[k] above
+ * its level's node count. */
+int frac_frq1_size(uint32_t width, uint32_t height, uint32_t max_size, uint32_t min_size, uint32_t transforms,
+                   uint32_t contrast_bits, uint32_t brightness_bits, const uint32_t splits[3], uint64_t* bytes);
 
 /* ---- FRC3: one colour frame — the Y, U and V plane streams in one container, decoded to RGB on the device ----
  * These four symbols were added after ABI 9 without changing FRAC_ABI_VERSION: probe for them by name

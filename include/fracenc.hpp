@@ -13,7 +13,8 @@
 //   Quantizer<T>        Frac::Quantizer (encode/Quantizer.hpp:7-45) as the built reference
 //                       computes it (value() with the FMA the compiler contracts)
 //   createUniformGrid / preclassify / encodeQuadtree / decode / decode_frc1 / frc1_info / decode_frq1 / frq1_info /
-//                       pack_frq1 / decode_frc3 / frc3_info — the C ABI entry points
+//                       pack_frq1 / decode_frc3 / frc3_info / quadtreeRate, rateSizes, rateFit, rateLeaves —
+//                       the C ABI entry points
 //   Engine's ABI 8/9 methods: an external HIP stream (void*), the tuple sink and 32-byte tuples,
 //                       frame streaming (setFrameAsync / setFrameDeviceAsync), 32-byte quadtree
 //                       leaves, per-run device times
@@ -140,7 +141,7 @@ public:
     ~Engine() { frac_destroy(ctx_); }
     Engine(const Engine&) = delete;
     Engine& operator=(const Engine&) = delete;
-    Engine(Engine&& o) noexcept : ctx_(std::exchange(o.ctx_, nullptr)), w_(o.w_), h_(o.h_) {}
+    Engine(Engine&& o) noexcept : ctx_(std::exchange(o.ctx_, nullptr)), w_(o.w_), h_(o.h_), rate_min_(o.rate_min_) {}
 
     frac_ctx* get() const { return ctx_; }
 
@@ -234,6 +235,49 @@ public:
         out.resize(n);
         return out;
     }
+    // The quadtree rate sweep (probe for the symbols by name when the library may be older): quadtreeRate
+    // searches the full tree once; rateSizes / rateFit / rateLeaves then answer for any split distance without a
+    // search, until the next setter, run or quadtree encode.
+    void quadtreeRate(uint32_t max_size, uint32_t min_size, frac_stats* st = nullptr)
+    {
+        check(frac_quadtree_rate_build(ctx_, max_size, min_size, st));
+        rate_min_ = min_size;
+    }
+    // per split distance the FRQ1 stream's bytes; leaves and splits ([n][4]) when asked for
+    std::vector<uint64_t> rateSizes(const std::vector<double>& split, uint32_t contrast_bits = 5,
+                                    uint32_t brightness_bits = 7, std::vector<uint32_t>* leaves = nullptr,
+                                    std::vector<uint32_t>* splits = nullptr)
+    {
+        std::vector<uint64_t> bytes(split.size());
+        if (leaves)
+            leaves->resize(split.size());
+        if (splits)
+            splits->resize(4 * split.size());
+        check(frac_quadtree_rate_sizes(ctx_, contrast_bits, brightness_bits, split.data(), split.size(), bytes.data(),
+                                       leaves ? leaves->data() : nullptr, splits ? splits->data() : nullptr));
+        return bytes;
+    }
+    struct RateFit {
+        double split_distance;
+        uint64_t bytes;
+        uint32_t leaves;
+    };
+    // the smallest split distance whose stream has at most max_bytes; throws when none fits
+    RateFit rateFit(uint64_t max_bytes, uint32_t contrast_bits = 5, uint32_t brightness_bits = 7)
+    {
+        RateFit f{};
+        check(frac_quadtree_rate_fit(ctx_, contrast_bits, brightness_bits, max_bytes, &f.split_distance, &f.bytes,
+                                     &f.leaves));
+        return f;
+    }
+    std::vector<frac_qt_leaf> rateLeaves(double split_distance)
+    {
+        size_t cap = rate_min_ ? (size_t)(w_ / rate_min_) * (h_ / rate_min_) : 0, n = 0;
+        std::vector<frac_qt_leaf> out(cap);
+        check(frac_quadtree_rate_leaves(ctx_, split_distance, out.data(), cap, &n));
+        out.resize(n < cap ? n : cap);
+        return out;
+    }
     // Decoder2::decode (encode/Encoder2.hpp:67-88); plane holds the caller's initial target
     // (main.cpp zeroes it) and receives the result.  Returns {iterations, rms}.
     std::pair<int, double> decode(const std::vector<frac_encode_item>& items, uint32_t w, uint32_t h,
@@ -314,6 +358,7 @@ private:
     }
     frac_ctx* ctx_ = nullptr;
     uint32_t w_ = 0, h_ = 0;
+    uint32_t rate_min_ = 0; // quadtreeRate's min_size: rateLeaves' worst-case capacity
 };
 
 // EncodingEngineCore2's role with batch claims.  One engine per entry of `devices` (a device
