@@ -243,6 +243,9 @@ def lib() -> C.CDLL:
                                              C.POINTER(C.c_uint64), C.POINTER(u32)]),
             "frac_quadtree_rate_leaves": (i32, [vp, C.c_double, vp, sz, C.POINTER(sz)]),
             "frac_frq1_size": (i32, [u32, u32, u32, u32, u32, u32, u32, C.POINTER(u32), C.POINTER(C.c_uint64)]),
+            "frac_quadtree_rate_stream": (i32, [vp, C.c_double, u32, u32, vp, sz, C.POINTER(sz)]),
+            "frac_encode_quadtree_stream": (i32, [vp, C.POINTER(FracQuadtreeParams), u32, u32, vp, sz,
+                                                  C.POINTER(sz), C.POINTER(FracStats)]),
             "frac_rgb_to_yuv_device": (i32, [vp, vp, u32, u32, u32, vp, u32, vp, u32, vp, u32]),
             "frac_rgb_to_yuv": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]),
             "frac_yuv_to_rgb_device": (i32, [vp, vp, u32, u32, u32, vp, u32, vp, u32, vp, u32]),
@@ -731,14 +734,46 @@ class Engine:
                                            plane.ctypes.data, plane.size, C.byref(it), C.byref(rms)))
         return plane, it.value, rms.value
 
-    def encode_quadtree_stream(self, max_size: int = 16, min_size: int = 4, split_distance: float = 10.0,
-                               contrast_bits: int = 5, brightness_bits: int = 7):
-        """The quadtree partition of the frame set on this engine as an FRQ1 stream: encode_quadtree(leaves=True)
-        and pack_frq1 with the engine's transforms and classifier flag.  Returns (bytes, summed stats dict)."""
-        leaves, st = self.encode_quadtree(max_size, min_size, split_distance, leaves=True)
+    def _frq1_buffer(self, max_size: int, min_size: int, contrast_bits: int, brightness_bits: int):
+        """A byte buffer kept across calls that holds any FRQ1 stream of this frame at these sizes and widths: every
+        node split (frq1_size) plus a dword of padding per section; 64 bytes where the library will refuse the
+        arguments anyway."""
         W, H = self._frame_wh
-        return pack_frq1(leaves, W, H, max_size, min_size, self._p.transforms, bool(self._p.use_classifier),
-                         contrast_bits, brightness_bits), st
+        try:
+            n0 = (W // max_size) * (H // max_size) if min(W, H) >= max_size > 0 else 0
+            cap = frq1_size(W, H, max_size, min_size, [n0, 4 * n0, 16 * n0], self._p.transforms, contrast_bits,
+                            brightness_bits) + 32
+        except FracError:
+            cap = 64
+        buf = getattr(self, "_frq1_buf", None)
+        if buf is None or len(buf) < cap:
+            buf = self._frq1_buf = np.empty(cap, dtype=np.uint8)
+        return buf
+
+    def encode_quadtree_stream(self, max_size: int = 16, min_size: int = 4, split_distance: float = 10.0,
+                               contrast_bits: int = 5, brightness_bits: int = 7, host_pack: bool = True):
+        """The quadtree partition of the frame set on this engine as an FRQ1 stream with the engine's transforms
+        and classifier flag.  host_pack=True: encode_quadtree(leaves=True) and pack_frq1 on the host.
+        host_pack=False: laid out, quantized and packed on the device (frac_encode_quadtree_stream: the leaves
+        never cross PCIe), the same bytes.  The host route is the default because the device route's 2.5 ms gain
+        was not outside the run-to-run spread of a frame whose search takes 0.5 s.
+        Returns (bytes, summed stats dict)."""
+        if host_pack:
+            leaves, st = self.encode_quadtree(max_size, min_size, split_distance, leaves=True)
+            W, H = self._frame_wh
+            return pack_frq1(leaves, W, H, max_size, min_size, self._p.transforms, bool(self._p.use_classifier),
+                             contrast_bits, brightness_bits), st
+        qp = FracQuadtreeParams(max_size, min_size, split_distance)
+        buf = self._frq1_buffer(max_size, min_size, contrast_bits, brightness_bits)
+        n, st = C.c_size_t(0), FracStats()
+        self._check(lib().frac_encode_quadtree_stream(self._ctx, C.byref(qp), contrast_bits, brightness_bits,
+                                                      buf.ctypes.data, len(buf), C.byref(n), C.byref(st)))
+        if n.value > len(buf):
+            raise FracError(f"encode_quadtree_stream: a stream of {n.value} bytes above its bound {len(buf)}")
+        stream = buf[: n.value].tobytes()
+        d = st.as_dict()
+        d["items"] = int.from_bytes(stream[24:28], "little")  # the header's n_leaves
+        return stream, d
 
     def encode_quadtree(self, max_size: int = 16, min_size: int = 4, split_distance: float = 10.0, out=None,
                         allow_short: bool = False, leaves: bool = False):
@@ -824,17 +859,34 @@ class Engine:
         self._check(lib().frac_quadtree_rate_leaves(self._ctx, split, buf.ctypes.data, cap, C.byref(n)))
         return buf[: min(n.value, cap)]
 
+    def rate_stream(self, split: float, contrast_bits: int = 5, brightness_bits: int = 7) -> bytes:
+        """The FRQ1 stream of the partition at `split` from the rate state (frac_quadtree_rate_stream): the bytes
+        pack_frq1 makes of rate_leaves(split), laid out, quantized and packed on the device — no search, and no
+        leaf crosses PCIe."""
+        mx, mn = getattr(self, "_rate_sizes", (0, 0))  # no build yet: the library refuses the call
+        buf = self._frq1_buffer(mx, mn, contrast_bits, brightness_bits)
+        n = C.c_size_t(0)
+        self._check(lib().frac_quadtree_rate_stream(self._ctx, split, contrast_bits, brightness_bits, buf.ctypes.data,
+                                                    len(buf), C.byref(n)))
+        if n.value > len(buf):
+            raise FracError(f"rate_stream: a stream of {n.value} bytes above its bound {len(buf)}")
+        return buf[: n.value].tobytes()
+
     def encode_quadtree_to_size(self, max_bytes: int, max_size: int = 16, min_size: int = 4,
-                                contrast_bits: int = 5, brightness_bits: int = 7):
+                                contrast_bits: int = 5, brightness_bits: int = 7, host_pack: bool = False):
         """The best quadtree partition of the frame set on this engine whose FRQ1 stream has at most max_bytes:
-        quadtree_rate + rate_fit + rate_leaves + pack_frq1.  Returns (bytes, info): info has the stats of the
-        full-tree search plus split_distance (the smallest that fits), bytes and items."""
+        quadtree_rate + rate_fit + rate_stream (host_pack=True: rate_leaves + pack_frq1 on the host, the same
+        bytes).  Returns (bytes, info): info has the stats of the full-tree search plus split_distance (the
+        smallest that fits), bytes and items."""
         info = self.quadtree_rate(max_size, min_size)
         t, size, n = self.rate_fit(max_bytes, contrast_bits, brightness_bits)
-        leaves = self.rate_leaves(t)
-        W, H = self._frame_wh
-        stream = pack_frq1(leaves, W, H, max_size, min_size, self._p.transforms, bool(self._p.use_classifier),
-                           contrast_bits, brightness_bits)
+        if host_pack:
+            leaves = self.rate_leaves(t)
+            W, H = self._frame_wh
+            stream = pack_frq1(leaves, W, H, max_size, min_size, self._p.transforms, bool(self._p.use_classifier),
+                               contrast_bits, brightness_bits)
+        else:
+            stream = self.rate_stream(t, contrast_bits, brightness_bits)
         info.update(split_distance=t, bytes=size, items=n)
         return stream, info
 

@@ -122,12 +122,14 @@ class ColorEncoder:
         return pack_frc3([e.pack_frc1(contrast_bits, brightness_bits) for e in self.engines], *self.frame_wh)
 
     def encode_quadtree_frc3(self, max_size: int = 16, min_size: int = 4, split_distance: float = 10.0,
-                             contrast_bits: int = 5, brightness_bits: int = 7):
+                             contrast_bits: int = 5, brightness_bits: int = 7, host_pack: bool | None = None):
         """After load(): each engine's encode_quadtree_stream (an FRQ1 stream per plane) in one FRC3 container.
+        host_pack: that method's switch between the host and the device packer (None: its default).
         Returns (container bytes, [summed stats dict] for Y, U, V)."""
         if self.planes is None:
             raise FracError("encode_quadtree_frc3: no frame loaded")
-        parts = [e.encode_quadtree_stream(max_size, min_size, split_distance, contrast_bits, brightness_bits)
+        kw = {} if host_pack is None else {"host_pack": host_pack}
+        parts = [e.encode_quadtree_stream(max_size, min_size, split_distance, contrast_bits, brightness_bits, **kw)
                  for e in self.engines]
         return pack_frc3([s for s, _ in parts], *self.frame_wh), [st for _, st in parts]
 

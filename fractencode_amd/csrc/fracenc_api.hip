@@ -48,6 +48,7 @@ using namespace fracenc;
 #include "fracenc_quadtree.hip"
 #include "fracenc_codec.hip"
 #include "fracenc_qtrate.hip"
+#include "fracenc_frq1pack.hip"
 
 namespace {
 

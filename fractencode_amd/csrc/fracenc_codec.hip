@@ -767,6 +767,24 @@ int frac_frq1_info(const uint8_t* stream, size_t len, struct frac_frq1_info* out
     return rc;
 }
 
+// the 64 header bytes of a stream of nl leaves quantized between mm = {cmin, cmax, bmin, bmax}
+static void frq1_header(uint8_t hdr[FRAC_FRQ1_HEADER_BYTES], uint32_t W, uint32_t H, uint32_t max_size,
+                        uint32_t min_size, uint32_t T, uint32_t stream_flags, uint32_t cbits, uint32_t bbits,
+                        uint32_t nl, const double mm[4])
+{
+    const uint16_t version = 1, flags = (uint16_t)stream_flags;
+    const uint32_t wh[2] = {W, H};
+    const uint8_t u8s[5] = {(uint8_t)max_size, (uint8_t)min_size, (uint8_t)T, (uint8_t)cbits, (uint8_t)bbits};
+    std::memset(hdr, 0, FRAC_FRQ1_HEADER_BYTES);
+    std::memcpy(hdr, "FRQ1", 4);
+    std::memcpy(hdr + 4, &version, 2);
+    std::memcpy(hdr + 6, &flags, 2);
+    std::memcpy(hdr + 8, wh, 8);
+    std::memcpy(hdr + 16, u8s, 5);
+    std::memcpy(hdr + 24, &nl, 4);
+    std::memcpy(hdr + 32, mm, 32);
+}
+
 int frac_pack_frq1(const frac_qt_leaf* leaves, size_t n, uint32_t W, uint32_t H, uint32_t max_size, uint32_t min_size,
                    uint32_t T, uint32_t stream_flags, uint32_t cbits, uint32_t bbits, uint8_t* out, size_t cap,
                    size_t* n_out)
@@ -875,18 +893,9 @@ int frac_pack_frq1(const frac_qt_leaf* leaves, size_t n, uint32_t W, uint32_t H,
     *n_out = total;
     if (!out)
         return FRAC_OK;
-    uint8_t hdr[FRAC_FRQ1_HEADER_BYTES] = {};
-    const uint16_t version = 1, flags = (uint16_t)stream_flags;
-    const uint32_t wh[2] = {W, H}, nl = (uint32_t)n;
-    const uint8_t u8s[5] = {(uint8_t)max_size, (uint8_t)min_size, (uint8_t)T, (uint8_t)cbits, (uint8_t)bbits};
+    uint8_t hdr[FRAC_FRQ1_HEADER_BYTES];
     const double mm[4] = {cmin, cmax, bmin, bmax};
-    std::memcpy(hdr, "FRQ1", 4);
-    std::memcpy(hdr + 4, &version, 2);
-    std::memcpy(hdr + 6, &flags, 2);
-    std::memcpy(hdr + 8, wh, 8);
-    std::memcpy(hdr + 16, u8s, 5);
-    std::memcpy(hdr + 24, &nl, 4);
-    std::memcpy(hdr + 32, mm, 32);
+    frq1_header(hdr, W, H, max_size, min_size, T, stream_flags, cbits, bbits, (uint32_t)n, mm);
     std::memcpy(out, hdr, std::min<size_t>(cap, FRAC_FRQ1_HEADER_BYTES));
     if (cap > FRAC_FRQ1_HEADER_BYTES && !body.empty())
         std::memcpy(out + FRAC_FRQ1_HEADER_BYTES, body.data(), std::min(cap, total) - FRAC_FRQ1_HEADER_BYTES);

@@ -100,6 +100,17 @@ struct Stream {
     operator hipStream_t() const { return s; }
 };
 
+// the device FRQ1 packer's section table (fracenc_frq1pack.hip: frq1_table writes it, frq1_pack reads it)
+struct Frq1Table {
+    uint32_t bm_word[4], rec_word[4]; // the level's bitmap / record section: first body dword
+    uint32_t reach0[4], leaf0[4];     // reached nodes / leaves before the level
+    uint32_t words, leaves;           // the body's dwords, the stream's leaves
+};
+struct Frq1Result {
+    Frq1Table t;
+    unsigned long long mm[4]; // max ~key(contrast), max key(contrast), the same of the brightness
+};
+
 } // namespace
 
 struct frac_ctx {
@@ -285,6 +296,7 @@ struct frac_ctx {
     struct QtRate {
         bool ready = false;                // a readable state: cleared by every setter, frac_run and the quadtree calls
         uint32_t W = 0, H = 0, max_size = 0, min_size = 0, levels = 0, transforms = 0;
+        bool classifier = false;           // the search ran classified (an FRQ1 header's flag bit 0)
         uint32_t nodes[4] = {0, 0, 0, 0};  // N_k of the full tree
         uint32_t off[5] = {0, 0, 0, 0, 0}; // first node of level k; off[levels] = the tree's node count
         uint32_t ndoms[4] = {0, 0, 0, 0};  // domains of level k: createUniformGrid(W, H, 2n, n)
@@ -308,6 +320,17 @@ struct frac_ctx {
         };
         Pinned<Result> h_res;              // mapped: the fit's answer, the emit's leaf count
     } rate;
+    // the device FRQ1 packer (fracenc_frq1pack.hip), sized by the tree's node counts and the worst-case body:
+    // per node of the level-major tree {reached, leaf} flags and their exclusive scan ([nodes + 1]), the search
+    // route's leaf number per node, the zeroed body, the leaves' four bound keys, the section table
+    struct Frq1Pack {
+        DBuf<unsigned long long> d_flag, d_rank, d_mm;
+        DBuf<uint32_t> d_slot, d_body;
+        DBuf<uint8_t> d_tmp; // hipcub's scratch
+        size_t tmp_bytes = 0;
+        DBuf<Frq1Table> d_tab;
+        Pinned<Frq1Result> h_res; // mapped: the table and the keys
+    } frq1pack;
     DBuf<uint8_t> d_sea_tmp;
     DBuf<unsigned long long> d_sea_count; // candidates the SEA search evaluated
     DBuf<unsigned long long> d_tp_evals;  // tiled form: per group, the (range, domain) pairs of its window

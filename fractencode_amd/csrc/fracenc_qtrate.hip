@@ -304,6 +304,7 @@ int frac_quadtree_rate_build(frac_ctx* c, uint32_t max_size, uint32_t min_size, 
     if ((n0 << (2 * (levels - 1))) * 4 / 3 >= (1ull << 31))
         return c->fail(FRAC_E_INVALID, "quadtree rate: the full tree has 2^31 nodes or more");
     R.W = W, R.H = H, R.max_size = max_size, R.min_size = min_size, R.levels = levels, R.transforms = T;
+    R.classifier = c->p.use_classifier != 0;
     for (uint32_t k = 0; k < 4; ++k) {
         R.nodes[k] = k < levels ? (uint32_t)(n0 << (2 * k)) : 0u;
         R.ndoms[k] = k < levels ? (uint32_t)frac_uniform_grid(W, H, 2 * side[k], side[k], nullptr, 0) : 0u;

@@ -122,8 +122,10 @@ bool qt_device_planned(const frac_ctx* c, const frac_quadtree_params* qp)
 constexpr uint32_t kQtShards = 32, kQtCounters = 9;
 
 int qt_encode_dev(frac_ctx* c, const frac_quadtree_params* qp, LevelGrid& level, frac_encode_item* out, size_t cap,
-                  size_t* n_out, frac_stats* stats, frac_qt_leaf* out32 = nullptr)
+                  size_t* n_out, frac_stats* stats, frac_qt_leaf* out32 = nullptr, bool keep32 = false)
 {
+    // keep32 (frac_encode_quadtree_stream): 32-byte leaves into d_qt_leaves32 and no further
+    const bool want32 = out32 || keep32;
     const uint32_t W = c->src.w, H = c->src.h, T = c->p.transforms;
     const int nb = c->p.use_classifier ? 7 : 1;
     const bool timing = (c->p.flags & FRAC_FLAG_TIMING) != 0;
@@ -131,7 +133,7 @@ int qt_encode_dev(frac_ctx* c, const frac_quadtree_params* qp, LevelGrid& level,
     HostTrace tr("quadtree (device-planned)");
     const size_t max_leaves = (size_t)(W / qp->min_size) * (H / qp->min_size);
     constexpr uint32_t kFirst = 2 * (kMaxBuckets + 1); // bucket bounds per level: domains, ranges
-    if (out32)
+    if (want32)
         FRAC_HIP(c, c->d_qt_leaves32.ensure(max_leaves));
     else
         FRAC_HIP(c, c->d_qt_leaves.ensure(max_leaves));
@@ -158,7 +160,7 @@ int qt_encode_dev(frac_ctx* c, const frac_quadtree_params* qp, LevelGrid& level,
     // (the emit kernels write them over PCIe while the later levels run); else into d_qt_leaves and one
     // copy at the end
     frac_encode_item* leaves = c->d_qt_leaves.ptr;
-    frac_qt_leaf* leaves32 = out32 ? c->d_qt_leaves32.ptr : nullptr;
+    frac_qt_leaf* leaves32 = want32 ? c->d_qt_leaves32.ptr : nullptr;
     uint32_t leaf_cap = (uint32_t)std::min<size_t>(max_leaves, 0xffffffffu);
     bool direct = false;
     void* const host_out = out32 ? static_cast<void*>(out32) : static_cast<void*>(out);
@@ -412,7 +414,7 @@ int qt_encode_dev(frac_ctx* c, const frac_quadtree_params* qp, LevelGrid& level,
 extern "C" {
 
 static int encode_quadtree_impl(frac_ctx* c, const frac_quadtree_params* qp, frac_encode_item* out,
-                                frac_qt_leaf* out32, size_t cap, size_t* n_out, frac_stats* stats);
+                                frac_qt_leaf* out32, size_t cap, size_t* n_out, frac_stats* stats, bool keep32 = false);
 
 int frac_encode_quadtree(frac_ctx* c, const frac_quadtree_params* qp, frac_encode_item* out, size_t cap,
                          size_t* n_out, frac_stats* stats)
@@ -420,8 +422,10 @@ int frac_encode_quadtree(frac_ctx* c, const frac_quadtree_params* qp, frac_encod
     return encode_quadtree_impl(c, qp, out, nullptr, cap, n_out, stats);
 }
 
-int frac_encode_quadtree_leaves(frac_ctx* c, const frac_quadtree_params* qp, frac_qt_leaf* out, size_t cap,
-                                size_t* n_out, frac_stats* stats)
+// frac_encode_quadtree_leaves; keep32 (frac_encode_quadtree_stream, fracenc_frq1pack.hip): every leaf stays in
+// d_qt_leaves32 on the device, out and cap are not used
+static int encode_quadtree_leaves_checked(frac_ctx* c, const frac_quadtree_params* qp, frac_qt_leaf* out, size_t cap,
+                                          size_t* n_out, frac_stats* stats, bool keep32)
 {
     if (!c)
         return FRAC_E_INVALID;
@@ -434,12 +438,18 @@ int frac_encode_quadtree_leaves(frac_ctx* c, const frac_quadtree_params* qp, fra
         return c->fail(FRAC_E_INVALID, "quadtree leaves: a frame side above 65535 does not fit the 16-bit origins");
     if (qp->min_size >= 2 && frac_uniform_grid(W, H, 2 * qp->min_size, qp->min_size, nullptr, 0) >= FRAC_QT_NO_DOMAIN)
         return c->fail(FRAC_E_INVALID, "quadtree leaves: the finest level has more domains than a 24-bit index holds");
-    return encode_quadtree_impl(c, qp, nullptr, out, cap, n_out, stats);
+    return encode_quadtree_impl(c, qp, nullptr, out, cap, n_out, stats, keep32);
+}
+
+int frac_encode_quadtree_leaves(frac_ctx* c, const frac_quadtree_params* qp, frac_qt_leaf* out, size_t cap,
+                                size_t* n_out, frac_stats* stats)
+{
+    return encode_quadtree_leaves_checked(c, qp, out, cap, n_out, stats, false);
 }
 
 // frac_encode_quadtree (out: 64-byte records) and frac_encode_quadtree_leaves (out32: 32-byte leaves)
 static int encode_quadtree_impl(frac_ctx* c, const frac_quadtree_params* qp, frac_encode_item* out,
-                                frac_qt_leaf* out32, size_t cap, size_t* n_out, frac_stats* stats)
+                                frac_qt_leaf* out32, size_t cap, size_t* n_out, frac_stats* stats, bool keep32)
 {
     if (!c)
         return FRAC_E_INVALID;
@@ -476,20 +486,30 @@ static int encode_quadtree_impl(frac_ctx* c, const frac_quadtree_params* qp, fra
     frac_stats total{};
     HostTrace tr("quadtree");
     qt_grids_for(c, W, H);
-    if (out32 &&!qt_device_planned(c, qp)) {
-        // the host-planned levels (other engines, tuning knobs): the records, then packed here
+    if ((out32 || keep32) && !qt_device_planned(c, qp)) {
+        // the host-planned levels (other engines, tuning knobs): the records, then packed here; keep32 uploads
+        // the packed leaves into d_qt_leaves32, where the device-planned levels leave theirs
+        if (keep32)
+            cap = (size_t)(W / qp->min_size) * (H / qp->min_size);
         std::vector<frac_encode_item> rec(cap);
         FRAC_TRY(encode_quadtree_impl(c, qp, cap ? rec.data() : nullptr, nullptr, cap, n_out, stats));
         const size_t m = std::min(cap, *n_out);
+        std::vector<frac_qt_leaf> up(keep32 ? m : 0);
+        frac_qt_leaf* dst = keep32 ? up.data() : out32;
         for (size_t i = 0; i < m; ++i) {
             const uint32_t n = rec[i].w;
-            out32[i] = qt_leaf_of(rec[i], W >= 2 * n ? (W - 2 * n) / n + 1 : 0u);
+            dst[i] = qt_leaf_of(rec[i], W >= 2 * n ? (W - 2 * n) / n + 1 : 0u);
+        }
+        if (keep32) {
+            FRAC_HIP(c, c->d_qt_leaves32.ensure(cap));
+            if (m)
+                FRAC_HIP(c, hipMemcpy(c->d_qt_leaves32.ptr, up.data(), m * sizeof(frac_qt_leaf), hipMemcpyHostToDevice));
         }
         return FRAC_OK;
     }
     LevelGrid level{c, c->doms_set};
     if (qt_device_planned(c, qp))
-        return qt_encode_dev(c, qp, level, out, cap, n_out, stats, out32);
+        return qt_encode_dev(c, qp, level, out, cap, n_out, stats, out32, keep32);
     // the host-planned levels start from the first level's grid (built here only: ≈40 µs of host time
     // before the device-planned frame's first launch)
     std::vector<frac_grid_item> pending = grid(qp->max_size, qp->max_size);

@@ -156,7 +156,8 @@ const char* frac_last_error(const frac_ctx* ctx);
  * planes changed between runs.  The results of a run are readable from that frac_run until the next call of
  * a setter — frac_set_params, frac_set_domains, frac_set_ranges, frac_set_frame, frac_set_planes,
  * frac_set_frame_device, frac_set_frame_device_async, frac_set_frame_async — or of frac_encode_quadtree /
- * frac_encode_quadtree_leaves / frac_quadtree_rate_build (which search lists of their own).  From such a call to
+ * frac_encode_quadtree_leaves / frac_encode_quadtree_stream / frac_quadtree_rate_build (which search lists of
+ * their own).  From such a call to
  * the next frac_run every reader — frac_fetch, frac_fetch_tuples, frac_copy_tuples_device,
  * frac_copy_results_device, frac_pack_frc1, frac_decode_results — returns FRAC_E_STATE, and
  * frac_device_results returns NULL: the old winners are never paired with the new parameters, domain list,
@@ -165,9 +166,9 @@ const char* frac_last_error(const frac_ctx* ctx);
  * frac_decode_frc1, frac_decode_frq1, frac_decode_frc3, frac_decode_frc3_device and the colour conversions
  * (frac_rgb_to_yuv, frac_rgb_to_yuv_device, frac_yuv_to_rgb, frac_yuv_to_rgb_device) leave the results readable.
  * The rate state of frac_quadtree_rate_build has the same life, from that call: it is readable
- * (frac_quadtree_rate_sizes, frac_quadtree_rate_fit, frac_quadtree_rate_leaves) until the next setter above,
- * frac_run, frac_encode_quadtree / frac_encode_quadtree_leaves or frac_quadtree_rate_build, after which its
- * readers return FRAC_E_STATE; the calls that leave a run's results readable leave it readable too, and so do
+ * (frac_quadtree_rate_sizes, frac_quadtree_rate_fit, frac_quadtree_rate_leaves, frac_quadtree_rate_stream) until
+ * the next setter above, frac_run, frac_encode_quadtree / frac_encode_quadtree_leaves /
+ * frac_encode_quadtree_stream or frac_quadtree_rate_build, after which its readers return FRAC_E_STATE; the calls that leave a run's results readable leave it readable too, and so do
  * its own readers. */
 int frac_set_params(frac_ctx* ctx, const frac_params* params);
 
@@ -486,6 +487,36 @@ int frac_quadtree_rate_leaves(frac_ctx* ctx, double split, frac_qt_leaf* out, si
  * its level's node count. */
 int frac_frq1_size(uint32_t width, uint32_t height, uint32_t max_size, uint32_t min_size, uint32_t transforms,
                    uint32_t contrast_bits, uint32_t brightness_bits, const uint32_t splits[3], uint64_t* bytes);
+
+/* ---- FRQ1 packed on the device: from the rate state, or from a search, the leaves never on the host ----
+ * These two symbols were added after ABI 9 without changing FRAC_ABI_VERSION: probe for them by name
+ * (dlsym) when the library may be older.
+ *
+ * Both return, byte for byte, what frac_pack_frq1 makes of the same leaves with the same widths (each in
+ * [2, 16], else FRAC_E_INVALID): one quantizer pair over every leaf, the domain-less ones included; a degenerate
+ * field coded as 0 with min == max in the header; index == the level's domain count for FRAC_QT_NO_DOMAIN; no
+ * bitmap bytes for a level without nodes; every section zero-padded to a dword; 64 bytes for a frame without
+ * level-0 ranges.  The split bitmaps, the sections' offsets (at counts only the device knows), the quantizer
+ * bounds, the codes and the bit-packing are computed on the device; the host receives the section table and the
+ * four bounds, writes the header, and copies exactly the body's bytes.  The header's transforms and flag bit 0
+ * (classifier) are the context's (the rate state's for the first call).  out is host memory, pageable or pinned;
+ * *n_out = the stream's size; min(cap, size) bytes are written (out may be NULL to query the size; the second
+ * call still searches).  A non-finite minimum or maximum fails the call with FRAC_E_INVALID, as
+ * frac_pack_frq1's check of every leaf does.  (Where a field's extreme is a zero that occurs with both signs, the
+ * header carries −0.0 as the minimum and +0.0 as the maximum, where the host packer keeps the first it met;
+ * the codes are the same.)
+ *  - frac_quadtree_rate_stream: the stream of the rate state's partition at `split`, i.e. of
+ *    frac_quadtree_rate_leaves(split).  A rate reader: FRAC_E_STATE without a readable rate state; it searches
+ *    nothing, leaves the state, the other readers' answers and a run's readable results alone, and ignores the
+ *    tuple sink.
+ *  - frac_encode_quadtree_stream: frac_encode_quadtree_leaves and frac_pack_frq1 in one call, with that call's
+ *    arguments, frame limits and statistics; it ends the last run's results and the rate state and consumes the
+ *    range list. */
+int frac_quadtree_rate_stream(frac_ctx* ctx, double split, uint32_t contrast_bits, uint32_t brightness_bits,
+                              uint8_t* out, size_t cap, size_t* n_out);
+int frac_encode_quadtree_stream(frac_ctx* ctx, const frac_quadtree_params* qp, uint32_t contrast_bits,
+                                uint32_t brightness_bits, uint8_t* out, size_t cap, size_t* n_out,
+                                frac_stats* stats);
 
 /* ---- FRC3: one colour frame — the Y, U and V plane streams in one container, decoded to RGB on the device ----
  * These four symbols were added after ABI 9 without changing FRAC_ABI_VERSION: probe for them by name
