@@ -169,6 +169,8 @@ def main():
     planes["crop480"] = np.ascontiguousarray(y[16:496, 16:496])
     planes["crop360"] = np.ascontiguousarray(y[100:460, 60:420])
     planes["crop400"] = np.ascontiguousarray(y[56:456, 56:456])
+    # a range side above 64 (more than one 4096-pixel chunk of the generic search): 390 = 6·65 = 3·130
+    planes["crop390"] = np.ascontiguousarray(y[60:450, 60:450])
     # Lenna RGB (the reference's own test input, decoded losslessly; checked against the
     # reference loader's planes below) and a seeded synthetic RGB frame with odd sizes
     from PIL import Image
@@ -237,6 +239,7 @@ def main():
         ("crop480_96to48_cls", "crop480", dict(src=96, tgt=48, T=4, cls=True)),
         ("crop400_80to40_thr", "crop400", dict(src=80, tgt=40, T=4, thr=110.0)),
         ("crop360_72to36_t8", "crop360", dict(src=72, tgt=36, T=8)),
+        ("crop390_130to65", "crop390", dict(src=130, tgt=65, T=4)),
     ]
     for name, pk, p in jobs:
         if not want(name):
