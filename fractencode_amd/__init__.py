@@ -246,6 +246,11 @@ def lib() -> C.CDLL:
             "frac_quadtree_rate_stream": (i32, [vp, C.c_double, u32, u32, vp, sz, C.POINTER(sz)]),
             "frac_encode_quadtree_stream": (i32, [vp, C.POINTER(FracQuadtreeParams), u32, u32, vp, sz,
                                                   C.POINTER(sz), C.POINTER(FracStats)]),
+            "frac_quadtree_rd_sizes": (i32, [vp, u32, u32, vp, sz, vp, vp, vp, vp]),
+            "frac_quadtree_rd_fit": (i32, [vp, u32, u32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                           C.POINTER(u32), C.POINTER(C.c_uint64)]),
+            "frac_quadtree_rd_leaves": (i32, [vp, u32, u32, C.c_uint64, vp, sz, C.POINTER(sz)]),
+            "frac_quadtree_rd_stream": (i32, [vp, C.c_uint64, u32, u32, vp, sz, C.POINTER(sz)]),
             "frac_rgb_to_yuv_device": (i32, [vp, vp, u32, u32, u32, vp, u32, vp, u32, vp, u32]),
             "frac_rgb_to_yuv": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]),
             "frac_yuv_to_rgb_device": (i32, [vp, vp, u32, u32, u32, vp, u32, vp, u32, vp, u32]),
@@ -872,13 +877,78 @@ class Engine:
             raise FracError(f"rate_stream: a stream of {n.value} bytes above its bound {len(buf)}")
         return buf[: n.value].tobytes()
 
+    def rd_sizes(self, lambdas, contrast_bits: int = 5, brightness_bits: int = 7):
+        """Per multiplier in `lambdas` (integers in [0, 2^32]) the rate–distortion-pruned partition of the rate
+        state's tree (frac_quadtree_rd_sizes; include/fracenc.h states the rule), every multiplier in one pass:
+        (bytes uint64 [n], leaves uint32 [n], per-level split counts uint32 [n, 4], distortion uint64 [n] —
+        16 × the leaves' summed squared error)."""
+        lam = np.ascontiguousarray(lambdas, dtype=np.uint64).reshape(-1)
+        n = len(lam)
+        size, leaves, s = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros((n, 4), np.uint32)
+        dist = np.zeros(n, np.uint64)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if n else None  # noqa: E731
+        self._check(lib().frac_quadtree_rd_sizes(self._ctx, contrast_bits, brightness_bits, ptr(lam), n, ptr(size),
+                                                 ptr(leaves), ptr(s), ptr(dist)))
+        return size, leaves, s, dist
+
+    def rd_fit(self, max_bytes: int, contrast_bits: int = 5, brightness_bits: int = 7):
+        """A multiplier whose pruned partition's FRQ1 stream has at most max_bytes while the multiplier below it
+        does not fit (or 0) → (lambda, bytes, leaves, distortion).  FracError when nothing fits."""
+        lam, size, leaves, dist = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+        self._check(lib().frac_quadtree_rd_fit(self._ctx, contrast_bits, brightness_bits, max_bytes, C.byref(lam),
+                                               C.byref(size), C.byref(leaves), C.byref(dist)))
+        return lam.value, size.value, leaves.value, dist.value
+
+    def rd_leaves(self, lam: int, contrast_bits: int = 5, brightness_bits: int = 7, out=None,
+                  allow_short: bool = False) -> np.ndarray:
+        """The QT_LEAF leaves of the pruned partition at multiplier `lam`, in canonical order, from the rate state
+        (no search).  `out` and allow_short as in rate_leaves."""
+        W, H = self._frame_wh
+        m = getattr(self, "_rate_sizes", (0, 0))[1]  # no build yet: the library refuses the call
+        cap = max((W // m) * (H // m), 1) if m else 1
+        if out is not None:
+            if out.dtype != QT_LEAF or not out.flags.c_contiguous or (len(out) < cap and not allow_short):
+                raise ValueError(f"out must be a contiguous QT_LEAF array of at least {cap} items")
+            buf, cap = out, len(out)
+        else:
+            buf = np.empty(cap, dtype=QT_LEAF)
+        n = C.c_size_t(0)
+        self._check(lib().frac_quadtree_rd_leaves(self._ctx, contrast_bits, brightness_bits, lam, buf.ctypes.data, cap,
+                                                  C.byref(n)))
+        return buf[: min(n.value, cap)]
+
+    def rd_stream(self, lam: int, contrast_bits: int = 5, brightness_bits: int = 7) -> bytes:
+        """The FRQ1 stream of the pruned partition at multiplier `lam` (frac_quadtree_rd_stream): the bytes
+        pack_frq1 makes of rd_leaves(lam), packed on the device like rate_stream."""
+        mx, mn = getattr(self, "_rate_sizes", (0, 0))  # no build yet: the library refuses the call
+        buf = self._frq1_buffer(mx, mn, contrast_bits, brightness_bits)
+        n = C.c_size_t(0)
+        self._check(lib().frac_quadtree_rd_stream(self._ctx, lam, contrast_bits, brightness_bits, buf.ctypes.data,
+                                                  len(buf), C.byref(n)))
+        if n.value > len(buf):
+            raise FracError(f"rd_stream: a stream of {n.value} bytes above its bound {len(buf)}")
+        return buf[: n.value].tobytes()
+
     def encode_quadtree_to_size(self, max_bytes: int, max_size: int = 16, min_size: int = 4,
-                                contrast_bits: int = 5, brightness_bits: int = 7, host_pack: bool = False):
+                                contrast_bits: int = 5, brightness_bits: int = 7, host_pack: bool = False,
+                                rd: bool = False):
         """The best quadtree partition of the frame set on this engine whose FRQ1 stream has at most max_bytes:
         quadtree_rate + rate_fit + rate_stream (host_pack=True: rate_leaves + pack_frq1 on the host, the same
         bytes).  Returns (bytes, info): info has the stats of the full-tree search plus split_distance (the
-        smallest that fits), bytes and items."""
+        smallest that fits), bytes and items.  rd=True: the rate–distortion-pruned partition instead of a split
+        distance's (quadtree_rate + rd_fit + rd_stream, or rd_leaves + pack_frq1 with host_pack); info then has
+        `lambda` and `distortion` in place of split_distance."""
         info = self.quadtree_rate(max_size, min_size)
+        if rd:
+            lam, size, n, dist = self.rd_fit(max_bytes, contrast_bits, brightness_bits)
+            if host_pack:
+                W, H = self._frame_wh
+                stream = pack_frq1(self.rd_leaves(lam, contrast_bits, brightness_bits), W, H, max_size, min_size,
+                                   self._p.transforms, bool(self._p.use_classifier), contrast_bits, brightness_bits)
+            else:
+                stream = self.rd_stream(lam, contrast_bits, brightness_bits)
+            info.update({"lambda": lam, "distortion": dist, "bytes": size, "items": n})
+            return stream, info
         t, size, n = self.rate_fit(max_bytes, contrast_bits, brightness_bits)
         if host_pack:
             leaves = self.rate_leaves(t)

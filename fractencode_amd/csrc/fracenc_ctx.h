@@ -331,6 +331,29 @@ struct frac_ctx {
         DBuf<Frq1Table> d_tab;
         Pinned<Frq1Result> h_res; // mapped: the table and the keys
     } frq1pack;
+    // rate–distortion pruning of the rate state's tree (fracenc_qtrd.hip): the nodes' integer distortions, made
+    // on the first RD call after a build, and the readers' multipliers, per-multiplier sums and answers.  Sized by
+    // the tree's node count or by the caller's n.
+    struct QtRd {
+        bool q_ready = false;             // d_q holds the current rate state's q(v); frac_quadtree_rate_build clears it
+        DBuf<uint32_t> d_q;               // [nodes] q(v) = llrint(d(v)·64n²), level-major like rate.d_nodes
+        DBuf<unsigned long long> d_lam;   // the multipliers of one launch
+        struct Acc {
+            unsigned long long dist;      // Σ q over the partition's leaves
+            uint32_t S[4];                // reached, splitting nodes per level
+        };
+        DBuf<Acc> d_acc;                  // [copies][n] per multiplier, one atomic per wave and quantity into a copy
+        DBuf<unsigned long long> d_bytes, d_dist; // frac_quadtree_rd_sizes: results out
+        DBuf<uint32_t> d_counts;          // [n][5]: leaves, splits[4]
+        struct Fit {
+            long long lo;                 // −1, or a multiplier whose stream does not fit
+            unsigned long long hi;        // a multiplier whose stream fits (once found)
+            unsigned long long bytes, dist, min_bytes;
+            uint32_t leaves, found;
+        };
+        DBuf<Fit> d_fit;                  // frac_quadtree_rd_fit: the interval between the rounds
+        Pinned<Fit> h_fit;                // mapped: its answer
+    } rd;
     DBuf<uint8_t> d_sea_tmp;
     DBuf<unsigned long long> d_sea_count; // candidates the SEA search evaluated
     DBuf<unsigned long long> d_tp_evals;  // tiled form: per group, the (range, domain) pairs of its window

@@ -3,13 +3,15 @@
 // (whose dkey and quantize it reuses, so the arithmetic is the one already pinned to the host packer).
 //
 // One packer over the level-major full-tree index (level k's N_k = 4^k·N_0 nodes from off[k], FRQ1's canonical
-// order) with two front ends that say, per node, whether a partition reaches it and whether it is a leaf there:
+// order) with three front ends that say, per node, whether a partition reaches it and whether it is a leaf there:
 //   frq1_state_rate   frac_quadtree_rate_stream: from the rate state's split keys and the split distance,
 //                     exactly as qtr_leaf_flags does; a node's record is its own slot of the state
 //   frq1_slots +      frac_encode_quadtree_stream: the search's leaves (d_qt_leaves32) scattered into their
 //   frq1_state_slots  full-tree slots, the inverse of qtr_ranges (the level-0 item, then one quadrant digit per
 //                     level); a node is reached when no ancestor is a leaf, a leaf when it has one itself
-// Both write one 64-bit flag per node, reached in the high word and leaf in the low one, and reduce the leaves'
+//   qrd_state         frac_quadtree_rd_stream (fracenc_qtrd.hip): from the rate state's integer distortions and a
+//                     multiplier, the bottom-up pruning's partition; a node's record is its own slot of the state
+// All write one 64-bit flag per node, reached in the high word and leaf in the low one, and reduce the leaves'
 // contrast and brightness to four order-preserving keys (a wave reduction, one atomic per wave and field).
 // Then, for either route:
 //   DeviceScan        one exclusive sum over the flags: the high word is the rank among reached nodes (the bit
@@ -235,11 +237,16 @@ Frq1Geom frq1_geom(uint32_t W, uint32_t H, uint32_t max_size, uint32_t min_size,
     return g;
 }
 
-// The stream of the partition the front end describes: rec = the rate state's nodes (n_rec unused) or the
-// search's n_rec leaves.  The caller has validated the arguments and set the device.
+// the RD route's front end (fracenc_qtrd.hip): the pruning's partition at `lambda` as flags and bounds
+int qrd_state(frac_ctx* c, uint32_t cbits, uint32_t bbits, unsigned long long lambda, unsigned long long* flag,
+              unsigned long long* mm);
+
+// The stream of the partition the front end describes: rec = the rate state's nodes (n_rec unused; by the split
+// keys rate_e at `split`, or with rd_lambda by the pruning at *rd_lambda) or the search's n_rec leaves.  The
+// caller has validated the arguments and set the device.
 int frq1_pack_stream(frac_ctx* c, Frq1Geom g, uint32_t W, uint32_t H, uint32_t max_size, uint32_t min_size, uint32_t T,
                      uint32_t stream_flags, const double* rate_e, double split, const frac_qt_leaf* rec, uint32_t n_rec,
-                     uint8_t* out, size_t cap, size_t* n_out)
+                     uint8_t* out, size_t cap, size_t* n_out, const unsigned long long* rd_lambda = nullptr)
 {
     auto& P = c->frq1pack;
     const uint32_t total = g.off[g.levels];
@@ -269,7 +276,9 @@ int frq1_pack_stream(frac_ctx* c, Frq1Geom g, uint32_t W, uint32_t H, uint32_t m
         FRAC_HIP(c, hipMemsetAsync(P.d_body.ptr, 0, (size_t)g.cap_words * sizeof(uint32_t), c->stream));
         const uint32_t blocks = (total + 1 + 255) / 256;
         const uint32_t* slot = nullptr;
-        if (rate_e) {
+        if (rd_lambda) {
+            FRAC_TRY(qrd_state(c, g.cbits, g.bbits, *rd_lambda, P.d_flag.ptr, P.d_mm.ptr));
+        } else if (rate_e) {
             frq1_state_rate<<<blocks, 256, 0, c->stream>>>(g, rate_e, split, rec, P.d_flag.ptr, P.d_mm.ptr);
         } else {
             FRAC_HIP(c, P.d_slot.ensure(total));

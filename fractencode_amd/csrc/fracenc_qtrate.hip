@@ -268,6 +268,53 @@ int qtr_reader_checks(frac_ctx* c, const char* who, uint32_t cbits, uint32_t bbi
     return FRAC_OK;
 }
 
+// The leaves a partition of the rate state's tree names, in canonical order, into the caller's memory: `flags`
+// launches what writes the [total + 1] leaf flags (the last one 0); then one scan and qtr_emit.  The caller has
+// run qtr_reader_checks.
+template <class Flags>
+int qtr_leaves_by(frac_ctx* c, frac_qt_leaf* out, size_t cap, size_t* n_out, Flags&& flags)
+{
+    auto& R = c->rate;
+    const uint32_t total = R.off[R.levels];
+    *n_out = 0;
+    if (!total)
+        return FRAC_OK;
+    // device memory and pinned host memory are written directly; pageable memory through d_out and one copy
+    frac_qt_leaf* dst = nullptr;
+    if (out && cap) {
+        hipPointerAttribute_t at{};
+        void* dp = nullptr;
+        if (hipPointerGetAttributes(&at, out) == hipSuccess) {
+            if (at.type == hipMemoryTypeDevice)
+                dst = out;
+            else if (at.type == hipMemoryTypeHost && hipHostGetDevicePointer(&dp, out, 0) == hipSuccess && dp)
+                dst = reinterpret_cast<frac_qt_leaf*>(dp);
+        }
+        (void)hipGetLastError(); // pageable memory is not an error
+    }
+    const bool staged = out && cap && !dst;
+    if (staged)
+        dst = R.d_out.ptr;
+    const uint32_t dcap = !out ? 0u : (uint32_t)std::min<size_t>(staged ? std::min(cap, R.d_out.cap) : cap, 0xffffffffu);
+    void* dres = nullptr;
+    FRAC_HIP(c, hipHostGetDevicePointer(&dres, R.h_res.ptr, 0));
+    const uint32_t blocks = (total + 1 + 255) / 256;
+    FRAC_TRY(flags(R.d_flag.ptr)); // [total + 1] leaf flags, the last one 0
+    size_t tb = R.tmp_bytes;
+    FRAC_HIP(c, hipcub::DeviceScan::ExclusiveSum(R.d_tmp.ptr, tb, R.d_flag.ptr, R.d_rank.ptr, (int)total + 1,
+                                                 c->stream));
+    qtr_emit<<<blocks, 256, 0, c->stream>>>(R.d_nodes.ptr, R.d_flag.ptr, R.d_rank.ptr, total, dst, dcap,
+                                            reinterpret_cast<frac_ctx::QtRate::Result*>(dres));
+    FRAC_HIP(c, hipGetLastError());
+    FRAC_HIP(c, hipStreamSynchronize(c->stream));
+    const uint32_t n_leaves = R.h_res->leaves;
+    *n_out = n_leaves;
+    if (staged && n_leaves)
+        FRAC_HIP(c, hipMemcpy(out, R.d_out.ptr, std::min<size_t>(dcap, n_leaves) * sizeof(frac_qt_leaf),
+                              hipMemcpyDeviceToHost));
+    return FRAC_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -300,6 +347,7 @@ int frac_quadtree_rate_build(frac_ctx* c, uint32_t max_size, uint32_t min_size, 
         return c->fail(FRAC_E_INVALID, "quadtree rate: source and target planes must have one size");
     auto& R = c->rate;
     R.ready = false;
+    c->rd.q_ready = false; // the RD readers' distortions (fracenc_qtrd.hip) are of the tree searched before
     const uint64_t n0 = frac_uniform_grid(W, H, max_size, max_size, nullptr, 0);
     if ((n0 << (2 * (levels - 1))) * 4 / 3 >= (1ull << 31))
         return c->fail(FRAC_E_INVALID, "quadtree rate: the full tree has 2^31 nodes or more");
@@ -484,45 +532,11 @@ int frac_quadtree_rate_leaves(frac_ctx* c, double split, frac_qt_leaf* out, size
     FRAC_TRY(qtr_reader_checks(c, "quadtree rate leaves", 2, 2));
     if (!n_out)
         return c->fail(FRAC_E_INVALID, "quadtree rate leaves: n_out is required");
-    auto& R = c->rate;
-    const uint32_t total = R.off[R.levels];
-    *n_out = 0;
-    if (!total)
+    return qtr_leaves_by(c, out, cap, n_out, [&](uint32_t* flag) {
+        const uint32_t total = c->rate.off[c->rate.levels];
+        qtr_leaf_flags<<<(total + 1 + 255) / 256, 256, 0, c->stream>>>(qtr_geom(c, 2, 2), c->rate.d_e.ptr, split, flag);
         return FRAC_OK;
-    // device memory and pinned host memory are written directly; pageable memory through d_out and one copy
-    frac_qt_leaf* dst = nullptr;
-    if (out && cap) {
-        hipPointerAttribute_t at{};
-        void* dp = nullptr;
-        if (hipPointerGetAttributes(&at, out) == hipSuccess) {
-            if (at.type == hipMemoryTypeDevice)
-                dst = out;
-            else if (at.type == hipMemoryTypeHost && hipHostGetDevicePointer(&dp, out, 0) == hipSuccess && dp)
-                dst = reinterpret_cast<frac_qt_leaf*>(dp);
-        }
-        (void)hipGetLastError(); // pageable memory is not an error
-    }
-    const bool staged = out && cap && !dst;
-    if (staged)
-        dst = R.d_out.ptr;
-    const uint32_t dcap = !out ? 0u : (uint32_t)std::min<size_t>(staged ? std::min(cap, R.d_out.cap) : cap, 0xffffffffu);
-    void* dres = nullptr;
-    FRAC_HIP(c, hipHostGetDevicePointer(&dres, R.h_res.ptr, 0));
-    const uint32_t blocks = (total + 1 + 255) / 256;
-    qtr_leaf_flags<<<blocks, 256, 0, c->stream>>>(qtr_geom(c, 2, 2), R.d_e.ptr, split, R.d_flag.ptr);
-    size_t tb = R.tmp_bytes;
-    FRAC_HIP(c, hipcub::DeviceScan::ExclusiveSum(R.d_tmp.ptr, tb, R.d_flag.ptr, R.d_rank.ptr, (int)total + 1,
-                                                 c->stream));
-    qtr_emit<<<blocks, 256, 0, c->stream>>>(R.d_nodes.ptr, R.d_flag.ptr, R.d_rank.ptr, total, dst, dcap,
-                                            reinterpret_cast<frac_ctx::QtRate::Result*>(dres));
-    FRAC_HIP(c, hipGetLastError());
-    FRAC_HIP(c, hipStreamSynchronize(c->stream));
-    const uint32_t n_leaves = R.h_res->leaves;
-    *n_out = n_leaves;
-    if (staged && n_leaves)
-        FRAC_HIP(c, hipMemcpy(out, R.d_out.ptr, std::min<size_t>(dcap, n_leaves) * sizeof(frac_qt_leaf),
-                              hipMemcpyDeviceToHost));
-    return FRAC_OK;
+    });
 }
 
 int frac_frq1_size(uint32_t W, uint32_t H, uint32_t max_size, uint32_t min_size, uint32_t T, uint32_t cbits,

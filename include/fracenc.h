@@ -166,7 +166,9 @@ const char* frac_last_error(const frac_ctx* ctx);
  * frac_decode_frc1, frac_decode_frq1, frac_decode_frc3, frac_decode_frc3_device and the colour conversions
  * (frac_rgb_to_yuv, frac_rgb_to_yuv_device, frac_yuv_to_rgb, frac_yuv_to_rgb_device) leave the results readable.
  * The rate state of frac_quadtree_rate_build has the same life, from that call: it is readable
- * (frac_quadtree_rate_sizes, frac_quadtree_rate_fit, frac_quadtree_rate_leaves, frac_quadtree_rate_stream) until
+ * (frac_quadtree_rate_sizes, frac_quadtree_rate_fit, frac_quadtree_rate_leaves, frac_quadtree_rate_stream, and the
+ * rate–distortion readers frac_quadtree_rd_sizes, frac_quadtree_rd_fit, frac_quadtree_rd_leaves,
+ * frac_quadtree_rd_stream) until
  * the next setter above, frac_run, frac_encode_quadtree / frac_encode_quadtree_leaves /
  * frac_encode_quadtree_stream or frac_quadtree_rate_build, after which its readers return FRAC_E_STATE; the calls that leave a run's results readable leave it readable too, and so do
  * its own readers. */
@@ -517,6 +519,52 @@ int frac_quadtree_rate_stream(frac_ctx* ctx, double split, uint32_t contrast_bit
 int frac_encode_quadtree_stream(frac_ctx* ctx, const frac_quadtree_params* qp, uint32_t contrast_bits,
                                 uint32_t brightness_bits, uint8_t* out, size_t cap, size_t* n_out,
                                 frac_stats* stats);
+
+/* ---- rate–distortion-optimal partitions from the rate state ----
+ * These four symbols were added after ABI 9 without changing FRAC_ABI_VERSION: probe for them by name
+ * (dlsym) when the library may be older.
+ *
+ * A split distance splits wherever one block is bad, whether or not its children are better.  These readers
+ * choose the partition of the rate state's full tree by bottom-up Lagrangian pruning instead, in exact unsigned
+ * 64-bit integer arithmetic (no result depends on a summation order):
+ *  - distortion of node v of level k (side n = max_size >> k): q(v) = llrint(d(v) · 64n²) with d(v) the distance
+ *    of the node's frac_qt_leaf — 16 × the block's summed squared error, an exact integer below 2^32 for every
+ *    record the search makes; 0 for a negative or NaN distance;
+ *  - bits: a leaf of level k < levels − 1 costs rb_k + 1 (its record, frac_frq1_size's record bits for these
+ *    widths, and its bitmap bit), a leaf of the last level rb_k, a split node 1;
+ *  - for a multiplier lambda (0 ≤ lambda ≤ 2^32): J(v) = q(v) + lambda·rb at the last level; above it
+ *    leafJ = q(v) + lambda·(rb_k + 1) and splitJ = lambda + Σ_children J(c); v splits exactly when
+ *    splitJ < leafJ (a tie keeps the leaf) and J(v) is the smaller of the two;
+ *  - level 0 is reached; a node is reached when its parent is reached and splits; a reached node that does not
+ *    split is a leaf.  With S_k the reached, splitting nodes of level k the stream's size is frac_frq1_size's
+ *    closed form; the distortion reported is Σ q over the leaves.
+ * At lambda = 2^32 nothing splits (q < 2^32, a split costs at least lambda more): the smallest stream there is.
+ * At lambda = 0 only the distortion counts.  The partitions nest as lambda grows.
+ *
+ * All four are rate readers, with frac_quadtree_rate_sizes' state rules: FRAC_E_STATE without a readable rate
+ * state; they search nothing, leave the state, each other's answers and a run's readable results alone and
+ * ignore the tuple sink.  Widths outside [2, 16] and a lambda above 2^32 are FRAC_E_INVALID before any launch.
+ * An empty state (no level-0 ranges) gives 64 bytes, no leaves, distortion 0 and fit 0.
+ *  - _sizes: for n multipliers the stream's bytes, its leaf count (leaves, may be NULL), the split counts S_k
+ *    (splits [n][4], may be NULL; 0 from the last level on) and the distortion (may be NULL), all multipliers
+ *    in one pass over the tree.
+ *  - _fit: a lambda in [0, 2^32] whose stream has at most max_bytes and whose predecessor lambda − 1 does not fit
+ *    (or lambda = 0) — the least fitting one wherever the size does not grow with lambda, which it does only
+ *    where the dword padding of two sections trades a word — with its size, leaf count and distortion (each
+ *    pointer may be NULL).  FRAC_E_INVALID when the stream at 2^32 is above max_bytes; the message names that
+ *    smallest size.
+ *  - _leaves: the partition's leaves in canonical order, every field as frac_quadtree_rate_leaves gives it for
+ *    the same nodes; out, cap and n_out as there (host, device or pinned host memory).
+ *  - _stream: byte for byte what frac_pack_frq1 makes of _leaves' output with these widths, packed on the device
+ *    as frac_quadtree_rate_stream packs; out, cap and n_out as there. */
+int frac_quadtree_rd_sizes(frac_ctx* ctx, uint32_t contrast_bits, uint32_t brightness_bits, const uint64_t* lambda,
+                           size_t n, uint64_t* bytes, uint32_t* leaves, uint32_t* splits, uint64_t* distortion);
+int frac_quadtree_rd_fit(frac_ctx* ctx, uint32_t contrast_bits, uint32_t brightness_bits, uint64_t max_bytes,
+                         uint64_t* lambda, uint64_t* bytes, uint32_t* leaves, uint64_t* distortion);
+int frac_quadtree_rd_leaves(frac_ctx* ctx, uint32_t contrast_bits, uint32_t brightness_bits, uint64_t lambda,
+                            frac_qt_leaf* out, size_t cap, size_t* n_out);
+int frac_quadtree_rd_stream(frac_ctx* ctx, uint64_t lambda, uint32_t contrast_bits, uint32_t brightness_bits,
+                            uint8_t* out, size_t cap, size_t* n_out);
 
 /* ---- FRC3: one colour frame — the Y, U and V plane streams in one container, decoded to RGB on the device ----
  * These four symbols were added after ABI 9 without changing FRAC_ABI_VERSION: probe for them by name
