@@ -267,6 +267,7 @@ def lib() -> C.CDLL:
             "frac_transform_index": (i32, [u32, u32, u32]),
             "frac_hit_limit": (C.c_int64, [C.c_double, u32]),
             "frac_debug_sort_chunk": (u32, []),
+            "frac_debug_resolve_group": (u32, []),
             "frac_debug_sort_pairs": (i32, [vp, vp, u32, vp, vp, u32, u32, vp, vp, vp, vp]),
             "frac_debug_bucket_tile": (u32, []),
             "frac_debug_bucket_self_tiles": (u32, []),

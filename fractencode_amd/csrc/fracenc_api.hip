@@ -174,6 +174,8 @@ const char* frac_last_error(const frac_ctx* ctx) { return ctx ? ctx->err.c_str()
 
 uint32_t frac_debug_sort_chunk(void) { return kTpSortChunk; }
 
+uint32_t frac_debug_resolve_group(void) { return kTpGrpItems; }
+
 // Test hook: the tiled form's sort (tp_sort_pairs) on host arrays, both sides through the same launches on the
 // current device's null stream, then a synchronous copy back.
 int frac_debug_sort_pairs(const uint32_t* keys, const uint32_t* vals, uint32_t n, const uint32_t* keys_b,

@@ -1566,28 +1566,52 @@ struct DftResolved {
     uint32_t bx = 0, bs1 = 0, bs2 = 0, sr1 = 0, sr2 = 0;
 };
 
-// ri: the slot's range (slot_range[slot], which the caller holds; < 0: padding)
+// What a slot's resolve loads by the slot alone: the search's merged word, 16Σr², the lane's orbits of the range
+// and, SORTED, the slot's two records (its row halves: lanes col and col + 32 of its block) and the block's group.
+// Issued together; the grouped resolve issues the next item's before it evaluates the current one.
+struct DftSlotLoads {
+    unsigned long long sb = 0ull;
+    uint32_t sa16 = 0;
+    uint4 r0 = make_uint4(0u, 0u, 0u, 0u), r1 = r0, rec0 = r0, rec1 = r0;
+    uint2 gw = make_uint2(0xffffffffu, 0u);
+};
+
+// (slot < nslots: in bounds whether or not the slot holds a range)
 template <bool SORTED>
-__device__ inline DftResolved resolve_dft_eval(const MfmaResolveArgs& a, uint32_t slot, int ri, int lane, bool flip)
+__device__ inline DftSlotLoads dft_slot_loads(const MfmaResolveArgs& a, uint32_t slot, int lane)
+{
+    DftSlotLoads ld;
+    ld.sb = a.slotbest ? a.slotbest[slot] : 0ull;
+    ld.sa16 = a.rconst[slot];
+    const uint4* rp4 = reinterpret_cast<const uint4*>(a.rorb + (size_t)slot * 32 + (lane & 3) * 8);
+    ld.r0 = rp4[0];
+    ld.r1 = rp4[1];
+    if constexpr (SORTED) {
+        const uint32_t blk = slot >> 5, col = slot & 31u;
+        ld.rec0 = a.rec[(size_t)blk * 64 + col];
+        ld.rec1 = a.rec[(size_t)blk * 64 + col + 32];
+        ld.gw = a.blk_group[blk];
+    }
+    return ld;
+}
+
+// ri: the slot's range (slot_range[slot], which the caller holds; < 0: padding); ld: the slot's loads.
+// ONE (SORTED): when a single lane holds a key after the evaluation — one row attains the target, the common
+// case — that lane's key and sums are read directly instead of through the 64-lane minimum; the same result.
+template <bool SORTED, bool ONE = false>
+__device__ inline DftResolved resolve_dft_eval(const MfmaResolveArgs& a, uint32_t slot, int ri, int lane, bool flip,
+                                               const DftSlotLoads& ld)
 {
     constexpr int PG = 16, T = 4; // T: the rotations evaluated per slot
     const uint32_t TK = a.T;      // the transforms of the keys (4, or 8 with the flipped copies)
     DftResolved res;
-    // the slot-only loads go out with the padding check's (slot < nslots: in bounds either way)
-    const unsigned long long sb = a.slotbest ? a.slotbest[slot] : 0ull;
-    const int64_t sa16 = (int64_t)a.rconst[slot];
+    const unsigned long long sb = ld.sb;
+    const int64_t sa16 = (int64_t)ld.sa16;
     const int i = lane >> 2, g = lane & 3;
-    const uint4* rp4 = reinterpret_cast<const uint4*>(a.rorb + (size_t)slot * 32 + g * (PG / 2));
-    const uint4 r0 = rp4[0], r1 = rp4[1];
+    const uint4 r0 = ld.r0, r1 = ld.r1;
     const uint32_t blk = slot >> 5, col = slot & 31u;
-    // SORTED: the slot's two records (its row halves: lanes col and col + 32 of its block) and the block's group
-    uint4 rec0 = make_uint4(0u, 0u, 0u, 0u), rec1 = rec0;
-    uint2 gw = make_uint2(0xffffffffu, 0u);
-    if constexpr (SORTED) {
-        rec0 = a.rec[(size_t)blk * 64 + col];
-        rec1 = a.rec[(size_t)blk * 64 + col + 32];
-        gw = a.blk_group[blk];
-    }
+    const uint4 rec0 = ld.rec0, rec1 = ld.rec1;
+    const uint2 gw = ld.gw;
     if (ri < 0)
         return res;
     // lane (i, g) holds orbits 4g..4g+3 of the range as pixel pairs (dft_range_prep) and meets
@@ -1807,20 +1831,33 @@ __device__ inline DftResolved resolve_dft_eval(const MfmaResolveArgs& a, uint32_
     }
     const unsigned long long mine = bestk;
     if constexpr (SORTED) {
+        const unsigned long long have = ONE ? __ballot(mine != kKeyNone) : ~0ull;
+        if (ONE && (have & (have - 1)) == 0ull) {
+            // at most one lane holds a key: it is the least (none: every lane's bestk is "none" already)
+            if (have) {
+                const int src = __ffsll((long long)have) - 1;
+                bestk = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(mine >> 32), src) << 32) |
+                        (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)mine, src);
+                bx = (uint32_t)__builtin_amdgcn_readlane((int)bx, src);
+                bs1 = (uint32_t)__builtin_amdgcn_readlane((int)bs1, src);
+                bs2 = (uint32_t)__builtin_amdgcn_readlane((int)bs2, src);
+            }
+        } else {
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned long long ok2 = ((unsigned long long)lane_xor((uint32_t)(bestk >> 32), lane, o) << 32) |
-                                           lane_xor((uint32_t)bestk, lane, o);
-            bestk = ok2 < bestk ? ok2 : bestk;
-        }
-        // the winner's sums: from the lane that evaluated it (keys are unique per (domain, transform)),
-        // broadcast through a ballot
-        const unsigned long long own = __ballot(mine == bestk && bestk != kKeyNone);
-        if (own) {
-            const int src = __ffsll((long long)own) - 1;
-            bx = (uint32_t)__builtin_amdgcn_readlane((int)bx, src);
-            bs1 = (uint32_t)__builtin_amdgcn_readlane((int)bs1, src);
-            bs2 = (uint32_t)__builtin_amdgcn_readlane((int)bs2, src);
+            for (int o = 32; o > 0; o >>= 1) {
+                const unsigned long long ok2 = ((unsigned long long)lane_xor((uint32_t)(bestk >> 32), lane, o) << 32) |
+                                               lane_xor((uint32_t)bestk, lane, o);
+                bestk = ok2 < bestk ? ok2 : bestk;
+            }
+            // the winner's sums: from the lane that evaluated it (keys are unique per (domain, transform)),
+            // broadcast through a ballot
+            const unsigned long long own = __ballot(mine == bestk && bestk != kKeyNone);
+            if (own) {
+                const int src = __ffsll((long long)own) - 1;
+                bx = (uint32_t)__builtin_amdgcn_readlane((int)bx, src);
+                bs1 = (uint32_t)__builtin_amdgcn_readlane((int)bs1, src);
+                bs2 = (uint32_t)__builtin_amdgcn_readlane((int)bs2, src);
+            }
         }
     }
     res.bestk = bestk;
@@ -1830,6 +1867,13 @@ __device__ inline DftResolved resolve_dft_eval(const MfmaResolveArgs& a, uint32_
     res.sr1 = sr1;
     res.sr2 = (uint32_t)sr2;
     return res;
+}
+
+// the same with the slot's loads issued here (one slot per wave)
+template <bool SORTED>
+__device__ inline DftResolved resolve_dft_eval(const MfmaResolveArgs& a, uint32_t slot, int ri, int lane, bool flip)
+{
+    return resolve_dft_eval<SORTED>(a, slot, ri, lane, flip, dft_slot_loads<SORTED>(a, slot, lane));
 }
 
 // range r's record from its resolved winner w (every lane holds the same after resolve_dft_eval); rg: the
@@ -1915,7 +1959,9 @@ __device__ inline void resolve_dft_pair(const MfmaResolveArgs& a, uint32_t slot,
 // the C3 finish 0.12 ms across PCIe.  Range order still has a price without the entry rows it once
 // scattered: a block's 32 slots no longer read their records, constants and orbit copies side by side, 0.035 ms of
 // the C3 finish with no sink or a device sink (§7.7), so a run without a host sink keeps the slot order.
-// kTpRangeOrder = false keeps the slot order everywhere.
+// kTpRangeOrder = false keeps the slot order everywhere.  Without a hit threshold both walks run in groups
+// (resolve_dft_groups below: ranges r0 … r0 + G − 1 write one contiguous block of the sink), 0.230 → 0.203 ms of the
+// C3 finish with a pinned sink and 0.197 → 0.176 with none (§7.14).
 constexpr bool kTpRangeOrder = true;
 
 // range r of the sorted route, range order: its slot from the inverse map (tp_build writes one per range)
@@ -1949,6 +1995,173 @@ __global__ void __launch_bounds__(256, 8) resolve_dft(MfmaResolveArgs a)
     } else {
         if (slot < a.nslots)
             resolve_dft_slot<SORTED>(a, slot, threadIdx.x & 63);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// resolve_dft_groups: the sorted route's resolve in groups of G consecutive items (ranges with a host sink, slots
+// otherwise, as kTpRangeOrder chooses), launched from launch_tp alone.  Only a range's tile evaluation fills a wave
+// (16 rows × 4 pixel quarters); its fit — fp64, two divisions — and its stores are per-range work that
+// resolve_dft<true> repeats in all 64 lanes.  Here a workgroup works in two phases:
+//   1  its waves evaluate the items (resolve_dft_eval<true>, unchanged arithmetic) and lane 0 leaves each item's
+//      {key, X, ΣD4 | Σr << 16, ΣD4², Σr², range, state} in LDS; a padding slot, an item past the end, a block
+//      without a group, an empty window all deposit and fall through, so every wave reaches the one barrier;
+//   2  lane k of wave 0 fits item k (fit_rstat_range_regs) and stores best_key and aux as one 8-byte store each.
+//      Range order: the group's records and tuples are the contiguous blocks [64·r0, 64·(r0 + n)) of the records
+//      and [32·r0, 32·(r0 + n)) of the sink; they are staged in LDS and leave as whole stores, 16 bytes a lane for
+//      the records and 8 for the tuples (the sink is 8-byte aligned and no more), lane l taking piece 64·j + l.
+//      A piece of an item whose record is not written here (fp32 regime, past the end) is not stored: no byte
+//      outside the block, none of a listed range's.  Slot order: each lane stores its own record and tuple.
+// The workgroup's shape was measured (C3, finish ms with a pinned sink / with none; resolve_dft<true> 0.230 / 0.197;
+// DESIGN §7.14): one item per wave and 16 waves 0.217 / 0.183, 8 waves 0.213 / 0.186, 4 waves 0.203 / 0.176 — the
+// tail of wave 0 holds a workgroup's wave slots, the fewer the better; 4 waves of 8 items each, the next item's
+// slot-level loads issued before the current one is evaluated, 0.250 / 0.202: the second set of loads does not fit
+// 64 registers (64 bytes of scratch).  Every shape: 64 VGPRs; scratch 0 but for that one.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kTpGrpWaves = 4u;   // waves per workgroup
+constexpr uint32_t kTpGrpPerWave = 1u; // items per wave
+constexpr uint32_t kTpGrpItems = kTpGrpWaves * kTpGrpPerWave; // G
+constexpr bool kTpGrpOne = true; // the winner read from its lane when one lane holds a key (resolve_dft_eval ONE)
+// runs with a hit threshold take the grouped form too (launch_tp); false: they keep resolve_dft<true>, whose waves
+// each end with their own first-hit walk instead of waiting at a barrier for the group's longest
+constexpr bool kTpGrpHits = false;
+static_assert(kTpGrpItems <= 64 && kTpGrpPerWave <= 64, "phase 2 is one wave, a lane per item");
+
+// workgroups for n items, the items of workgroup b, and the 16- or 8-byte pieces of a group's staged block
+__host__ __device__ constexpr uint32_t tp_grp_grid(uint32_t n)
+{
+    return n / kTpGrpItems + (n % kTpGrpItems != 0u ? 1u : 0u);
+}
+__host__ __device__ constexpr uint32_t tp_grp_count(uint32_t n, uint32_t b)
+{
+    return b >= tp_grp_grid(n) ? 0u : (n - b * kTpGrpItems < kTpGrpItems ? n - b * kTpGrpItems : kTpGrpItems);
+}
+constexpr uint32_t kTpGrpPieces = kTpGrpItems * 4u; // a record is four 16-byte pieces, a tuple four 8-byte ones
+constexpr uint32_t kTpGrpPasses = (kTpGrpPieces + 63u) / 64u;
+static_assert(tp_grp_grid(0u) == 0u && tp_grp_grid(1u) == 1u && tp_grp_grid(kTpGrpItems) == 1u &&
+                  tp_grp_grid(kTpGrpItems + 1u) == 2u &&
+                  tp_grp_grid(0xffffffffu) == (uint32_t)((0xffffffffull + kTpGrpItems - 1u) / kTpGrpItems),
+              "grid size");
+static_assert(tp_grp_count(0u, 0u) == 0u && tp_grp_count(1u, 0u) == 1u && tp_grp_count(kTpGrpItems, 0u) == kTpGrpItems &&
+                  tp_grp_count(kTpGrpItems, 1u) == 0u && tp_grp_count(kTpGrpItems + 1u, 1u) == 1u &&
+                  tp_grp_count(0xffffffffu, tp_grp_grid(0xffffffffu) - 1u) == (0xffffffffu - 1u) % kTpGrpItems + 1u,
+              "items of a group");
+static_assert((uint64_t)(tp_grp_grid(0xffffffffu) - 1u) * kTpGrpItems +
+                      tp_grp_count(0xffffffffu, tp_grp_grid(0xffffffffu) - 1u) == 0xffffffffull,
+              "the last group's items end at n: no index of an item wraps");
+static_assert(kTpGrpPasses * 64u >= kTpGrpPieces && (kTpGrpPasses - 1u) * 64u < kTpGrpPieces &&
+                  sizeof(frac_encode_item) == 64 && sizeof(frac_tuple) == 32 && sizeof(RangeAux) == 8,
+              "staged pieces");
+
+template <bool BY_RANGE>
+__global__ void __launch_bounds__(kTpGrpWaves * 64, 8) resolve_dft_groups(MfmaResolveArgs a)
+{
+    constexpr uint32_t G = kTpGrpItems;
+    __shared__ uint4 dep[G][2];
+    __shared__ uint4 srec[BY_RANGE ? kTpGrpPieces : 1];
+    __shared__ uint2 stup[BY_RANGE ? kTpGrpPieces : 1];
+    apply_plan(a);
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t base = blockIdx.x * G, cnt = tp_grp_count(BY_RANGE ? a.nr : a.nslots, blockIdx.x);
+    // ---- phase 1: this wave's items k = j·waves + wave; lane j first loads item j's slot and range
+    uint32_t vslot = 0u;
+    int vri = -1;
+    if ((uint32_t)lane < kTpGrpPerWave) {
+        const uint32_t k = (uint32_t)lane * kTpGrpWaves + wave;
+        if (k < cnt) {
+            if constexpr (BY_RANGE) {
+                vslot = a.range_slot[base + k];
+                vri = vslot < a.nslots ? (int)(base + k) : -1;
+            } else {
+                vslot = base + k;
+                vri = a.slot_range[vslot];
+            }
+        }
+    }
+    uint32_t slot = (uint32_t)__builtin_amdgcn_readlane((int)vslot, 0);
+    int ri = __builtin_amdgcn_readlane(vri, 0);
+    DftSlotLoads ld;
+    if (ri >= 0)
+        ld = dft_slot_loads<true>(a, slot, lane);
+#pragma unroll 1
+    for (uint32_t j = 0; j < kTpGrpPerWave; ++j) {
+        // the next item's slot-level loads go out before this one is evaluated
+        uint32_t nslot = 0u;
+        int nri = -1;
+        DftSlotLoads nld;
+        if (j + 1u < kTpGrpPerWave) {
+            nslot = (uint32_t)__builtin_amdgcn_readlane((int)vslot, (int)(j + 1u));
+            nri = __builtin_amdgcn_readlane(vri, (int)(j + 1u));
+            if (nri >= 0)
+                nld = dft_slot_loads<true>(a, nslot, lane);
+        }
+        // (ri < 0 — a padding slot, an item past the end: the default, nothing read)
+        const DftResolved w = resolve_dft_eval<true, kTpGrpOne>(a, slot, ri, lane, false, ld);
+        if (lane == 0) {
+            const uint32_t k = j * kTpGrpWaves + wave;
+            dep[k][0] = make_uint4((uint32_t)w.bestk, (uint32_t)(w.bestk >> 32), w.bx, w.bs1 | (w.sr1 << 16));
+            dep[k][1] = make_uint4(w.bs2, w.sr2, (uint32_t)ri, ri >= 0 ? 1u : 0u);
+        }
+        slot = nslot;
+        ri = nri;
+        ld = nld;
+    }
+    __syncthreads();
+    // ---- phase 2: wave 0, lane k fits item k
+    if (wave != 0u)
+        return;
+    // The fit's arguments are read here from the kernel-argument segment (the one by-value argument lies at its
+    // start): loaded at entry with the rest they would be held in scalar registers across the evaluation, which
+    // has none to spare, and spilled to vector lanes.
+    const MfmaResolveArgs& ka =
+        *reinterpret_cast<const MfmaResolveArgs*>((const void*)__builtin_amdgcn_kernarg_segment_ptr());
+    const FitArgs& fit = ka.fit;
+    FitRegs f;
+    f.kind = kFitSkip;
+    uint32_t r = 0u;
+    if ((uint32_t)lane < G) {
+        const uint4 d0 = dep[lane][0], d1 = dep[lane][1];
+        if (d1.w) {
+            r = d1.z;
+            const unsigned long long key = ((unsigned long long)d0.y << 32) | d0.x;
+            f = fit_rstat_range_regs<8>(fit, r, key, make_uint4(d0.z, d0.w, d1.x, d1.y), fit.ranges[r]);
+            reinterpret_cast<uint2*>(ka.best_key)[r] = make_uint2(d0.x, d0.y);
+            reinterpret_cast<uint2*>(fit.aux)[r] = f.aux;
+        }
+    }
+    if constexpr (BY_RANGE) {
+        if (f.kind == kFitRecord) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                srec[lane * 4 + q] = f.q[q];
+                stup[lane * 4 + q] = fit_tuple_piece(f, q);
+            }
+        }
+        const unsigned long long written = __ballot(f.kind == kFitRecord); // bit k: item k's record leaves here
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");            // (one wave: its LDS writes are done)
+        __builtin_amdgcn_wave_barrier();
+        uint4* out4 = reinterpret_cast<uint4*>(fit.out + base);
+        uint2* tup2 = reinterpret_cast<uint2*>(fit.tuples + base);
+#pragma unroll
+        for (uint32_t j = 0; j < kTpGrpPasses; ++j) {
+            const uint32_t u = 64u * j + (uint32_t)lane; // piece u of the block belongs to item u / 4
+            if (u < kTpGrpPieces && ((written >> (u >> 2)) & 1ull)) {
+                out4[u] = srec[u];
+                tup2[u] = stup[u];
+            }
+        }
+    } else if (f.kind == kFitRecord) {
+        uint4* out4 = reinterpret_cast<uint4*>(fit.out + r);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            out4[q] = f.q[q];
+        if (fit.tuples) {
+            uint2* tup2 = reinterpret_cast<uint2*>(fit.tuples + r);
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                tup2[q] = fit_tuple_piece(f, q);
+        }
     }
 }
 

@@ -619,6 +619,73 @@ __device__ inline void fit_rstat_range_wave(const FitArgs& a, uint32_t r, unsign
         a.aux[r] = RangeAux{p, hit ? (uint32_t)kAuxHit : 0u};
 }
 
+// fit_rstat_range by one lane with its outputs left in registers (the grouped resolve, resolve_dft_groups: lane k
+// fits item k and the group's records and tuples leave as whole blocks): the record as its four uint4 {the range,
+// {distance, contrast}, {brightness, transform, _pad}, the domain}, the tuple as its four 8-byte pairs, the aux
+// word, and which of them apply (the tuple's pieces repeat the record's words: fit_tuple_piece).  kFitSkip: nothing (the lane holds no range); kFitListed: fp32 regime, listed
+// here, the aux word alone (fallback_grid writes the record); kFitRecord: all of them (the default record too).
+// The same expressions as fit_rstat_range.
+enum : uint32_t { kFitSkip = 0, kFitListed = 1, kFitRecord = 2 };
+struct FitRegs {
+    uint4 q[4];
+    uint32_t dom;
+    uint2 aux;
+    uint32_t kind;
+};
+
+// 8-byte piece i of the tuple {domain, transform, s, o, distance} of a fitted record
+__device__ inline uint2 fit_tuple_piece(const FitRegs& f, int i)
+{
+    return i == 0   ? make_uint2(f.dom, f.q[2].z)
+           : i == 1 ? make_uint2(f.q[1].z, f.q[1].w)
+           : i == 2 ? make_uint2(f.q[2].x, f.q[2].y)
+                    : make_uint2(f.q[1].x, f.q[1].y);
+}
+
+template <int N>
+__device__ inline FitRegs fit_rstat_range_regs(const FitArgs& a, uint32_t r, unsigned long long key, const uint4& st,
+                                               const frac_grid_item& rg)
+{
+    constexpr int NN = N * N;
+    FitRegs f;
+    f.kind = kFitRecord;
+    f.q[0] = make_uint4(rg.x, rg.y, rg.w, rg.h);
+    if (key == kKeyNone) { // write_default
+        const double dflt = 100000.0;
+        const uint32_t e0 = (uint32_t)__double2loint(dflt), e1 = (uint32_t)__double2hiint(dflt);
+        f.q[1] = make_uint4(e0, e1, 0u, 0u);
+        f.q[2] = f.q[3] = make_uint4(0u, 0u, 0u, 0u);
+        f.dom = FRAC_NO_DOMAIN;
+        f.aux = make_uint2(0u, (uint32_t)kAuxEmpty);
+        return f;
+    }
+    const uint32_t p = key_pos(key);
+    const bool hit = (key >> 63) == 0;
+    const long long err = hit ? 0 : (long long)((key >> 27) & 0xffffffffull);
+    const int t = hit ? (int)(key & 7u) : (int)(a.T - 1 - (uint32_t)(key & 7u));
+    if (!hit && err >= kExactLimit) { // fp32 regime: listed; fallback_grid writes the record
+        f.kind = kFitListed;
+        f.aux = make_uint2(p, (uint32_t)kAuxFallback);
+        a.fb_list[atomicAdd(a.fb_count, 1u)] = r;
+        return f;
+    }
+    const uint32_t dom = a.porig[p];
+    const frac_grid_item d = a.doms[dom];
+    const long long X = st.x, sD = st.y & 0xffffu, sA = st.y >> 16, sD2 = st.z, sA2 = st.w;
+    const long long S16 = 16 * sA2 - 8 * X + sD2;
+    const double dist = ((double)S16 * 0.0625) / (double)(d.w * d.h);
+    const FitCoef c = fit_coef((double)sA, (double)sA2, (double)sD * 0.25, (double)X * 0.25, (double)NN, a.smax);
+    const uint32_t s0 = (uint32_t)__double2loint(c.s), s1 = (uint32_t)__double2hiint(c.s);
+    const uint32_t b0 = (uint32_t)__double2loint(c.br), b1 = (uint32_t)__double2hiint(c.br);
+    const uint32_t e0 = (uint32_t)__double2loint(dist), e1 = (uint32_t)__double2hiint(dist);
+    f.q[1] = make_uint4(e0, e1, s0, s1);
+    f.q[2] = make_uint4(b0, b1, (uint32_t)t, 0u);
+    f.q[3] = make_uint4(d.x, d.y, d.w, d.h);
+    f.dom = dom;
+    f.aux = make_uint2(p, hit ? (uint32_t)kAuxHit : 0u);
+    return f;
+}
+
 template <int N>
 __global__ void __launch_bounds__(256) fit_rstat(FitArgs a, const uint4* __restrict__ rstat)
 {

@@ -904,8 +904,17 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
     v.flip_slots = 0;
     if (c->dft_copies != 1 || c->p.transforms != 4)
         return c->fail(FRAC_E_STATE, "SEA tiled form: T = 4 only (resolve_dft<true> has no flipped copies)");
-    // tuples bound for host memory leave in range order (one wave per range), else one wave per slot
-    if (kTpRangeOrder && v.fit.tuples && c->tuple_sink_host)
+    // tuples bound for host memory leave in range order, else the walk is in slot order; in groups of
+    // kTpGrpItems with one fit per range (resolve_dft_groups), or — kTpGrpHits false — with a hit threshold
+    // (H > 0; at H = 0 a hit is an exact match) one wave per item: the first-hit walks of a group's items differ
+    // widely in length
+    const bool by_range = kTpRangeOrder && v.fit.tuples && c->tuple_sink_host;
+    if (kTpGrpHits || c->hitH <= 0) {
+        if (by_range)
+            resolve_dft_groups<true><<<std::max(1u, tp_grp_grid(nr)), kTpGrpWaves * 64, 0, c->stream>>>(v);
+        else
+            resolve_dft_groups<false><<<std::max(1u, tp_grp_grid(v.nslots)), kTpGrpWaves * 64, 0, c->stream>>>(v);
+    } else if (by_range)
         resolve_dft<true, true><<<std::max(1u, (nr + 3) / 4), 256, 0, c->stream>>>(v);
     else
         resolve_dft<true><<<std::max(1u, (v.nslots + 3) / 4), 256, 0, c->stream>>>(v);

@@ -639,8 +639,11 @@ int64_t frac_hit_limit(double rms_threshold, uint32_t n);
  * frac_debug_sort_pairs runs the tiled SEA form's stable sort (csrc/fracenc_tpsort.hip) on host arrays: the
  * (key, value) pairs of two sides, n and n_b of them (either may be 0), go through the same launches on the
  * current device and come back sorted by the low `bits` key bits (1..32), equal keys in input order.
- * frac_debug_sort_chunk is the sort's items per workgroup. */
+ * frac_debug_sort_chunk is the sort's items per workgroup.
+ * frac_debug_resolve_group is the number of consecutive ranges (or slots) one workgroup of the tiled form's
+ * grouped resolve takes (csrc/fracenc_dft.hip, resolve_dft_groups). */
 uint32_t frac_debug_sort_chunk(void);
+uint32_t frac_debug_resolve_group(void);
 int frac_debug_sort_pairs(const uint32_t* keys, const uint32_t* vals, uint32_t n, const uint32_t* keys_b,
                           const uint32_t* vals_b, uint32_t n_b, uint32_t bits, uint32_t* out_keys,
                           uint32_t* out_vals, uint32_t* out_keys_b, uint32_t* out_vals_b);
