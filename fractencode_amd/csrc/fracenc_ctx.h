@@ -241,7 +241,8 @@ struct frac_ctx {
     std::vector<uint2> tp_blk_group;
     DBuf<uint4> d_tp_groups;
     DBuf<uint2> d_tp_blk_group, d_tp_tile_sd, d_tp_blk_sr;
-    DBuf<uint32_t> d_tp_blk_u, d_tp_pairs, d_tp_row_of;
+    DBuf<uint32_t> d_tp_blk_u, d_tp_pairs;
+    DBuf<uint8_t> d_tp_rpix;   // [nr][64] the ranges' pixels in range order (tp_keys → tp_prep)
     DBuf<uint32_t> d_tp_order; // [groups] the windowed search's work item per workgroup, longest window first (tp_plan)
     DBuf<uint4> d_tp_rec;     // [nblocks·64] search_dft CHUNKED's record per block and lane (DftArgs::rec)
     struct TpTotals {

@@ -240,27 +240,21 @@ struct DftDomainBuildArgs {
     uint32_t* pool;             // [P][32] packed u16 pairs of D4
     int32_t* negsd2;            // [P]
     uint32_t* tpool;            // [ntiles*32][32] the same rows in tile order, orbit order (resolve_dft)
-    const uint32_t* row_of = nullptr; // BYPOS: [P] tile row of each pool position (tp_build)
-    uint32_t npos = 0;                // BYPOS: P
 };
 
 // pair_sums: fracenc_kernels.hip (pool_build)
 
-// BYPOS (the SEA tiled form, whose tiles hold domains in ΣD4 order): one thread per pool
-// position in domain order, so neighbouring threads read overlapping plane rows, and the
-// outputs are scattered to the position's tile row; tp_build writes the padding rows and
-// zeroes the tile guards, which are then raised with atomics.
 // F5: the five-MFMA form's fragments [s_b + u_b | s_b − u_b | γ | γ − δ | −δ − γ] (kDft5)
-template <bool BYPOS = false, bool F5 = false>
+template <bool F5 = false>
 __device__ __forceinline__ void dft_domain_build_at(uint32_t tid, const MfmaDomainPrepArgs& a, const DftDomainBuildArgs& s,
                                                     uint2* __restrict__ tguard, int32_t* __restrict__ trmax)
 {
     constexpr int NN = 64, NO = 16, KS = F5 ? 5 : 4;
-    if (tid >= (BYPOS ? s.npos : a.ntiles * 32u))
+    if (tid >= a.ntiles * 32u)
         return;
-    const uint32_t gid = BYPOS ? s.row_of[tid] : tid;
+    const uint32_t gid = tid;
     const uint32_t tile = gid >> 5, row = gid & 31u;
-    const int p = BYPOS ? (int)tid : a.tile_pos[gid];
+    const int p = a.tile_pos[gid];
     uint32_t w[NN / 2];
     if (p >= 0) {
         const frac_grid_item d = s.doms[s.porig[p]];
@@ -363,11 +357,6 @@ __device__ __forceinline__ void dft_domain_build_at(uint32_t tid, const MfmaDoma
     const uint32_t h = (row >> 2) & 1u, i = (row & 3u) + 4u * (row >> 3);
     a.dconst[(size_t)tile * (kDftCS * 4) + h * 16 + i] = __float_as_uint(ny);
     uint32_t gx = p >= 0 ? (uint32_t)((F5 ? 2 : 4) * dinf) : 0u, gy = p >= 0 ? (uint32_t)sb2 : 0u;
-    if constexpr (BYPOS) {
-        atomicMax(&tguard[tile].x, gx);
-        atomicMax(&tguard[tile].y, gy);
-        return;
-    }
     // the tile's guard terms over its valid rows: a 32-lane maximum (whole tiles leave together
     // above), one writer per tile
 #pragma unroll
@@ -390,28 +379,51 @@ __device__ __forceinline__ void dft_domain_build_at(uint32_t tid, const MfmaDoma
 // guard terms meet in a lane-pair shuffle.  On a small frame the single-thread chain per row ran one
 // wave per CU on a quarter of the CUs (C2: 16 workgroups); this halves the chain and doubles the waves.
 // A tile's 32 rows are one wave's 64 lanes, so the tile guards stay a wave reduction.
-// BYPOS (the SEA tiled form, as dft_domain_build_at's): the lane pair takes a pool position in domain order and
-// scatters the tile-order outputs to its row (row_of); a tile's rows are then in many waves, so the guards are
-// raised with atomics over the zeroes tp_build wrote (no padding row comes here, and no trmax: the tiled form's
-// thresholds are formed from the finished guards by tp_seed_windows, fracenc_tp.hip).
+// ROWS (the SEA tiled form's tp_prep, fracenc_tp.hip): the pool rows and −ΣD4² are already there, written in pool
+// order by the pixel pass before the sort (tp_keys), so the lane pair reads the plane not at all: lane h loads its
+// 64-byte half of pool[p] — p in ΣD4 order, the route's one gather per domain, a whole 128-byte line per pair —
+// and writes neither.  Everything after the load is the same code.  Its row stage is the caller's (lds, 128 rows of
+// kDbRowWords words), which tp_prep shares with its range half.
 constexpr uint32_t kDbRowWords = 33; // LDS words per row: 32 + 1 of padding (rows in distinct banks)
-template <bool F5, bool BYPOS = false>
+template <bool F5, bool ROWS = false>
 __device__ __forceinline__ void dft_domain_build_pair_at(uint32_t tid2, const MfmaDomainPrepArgs& a,
                                                          const DftDomainBuildArgs& s, uint2* __restrict__ tguard,
-                                                         int32_t* __restrict__ trmax)
+                                                         int32_t* __restrict__ trmax, uint32_t* lds = nullptr)
 {
     constexpr int KS = F5 ? 5 : 4;
-    __shared__ uint32_t rows[128 * kDbRowWords]; // 256 threads = 128 rows
+    uint32_t* rows; // 256 threads = 128 rows
+    if constexpr (ROWS) {
+        rows = lds;
+    } else {
+        __shared__ uint32_t own[128 * kDbRowWords];
+        rows = own;
+    }
     const uint32_t hh = tid2 & 1u;
-    if ((tid2 >> 1) >= (BYPOS ? s.npos : a.ntiles * 32u)) // whole tiles (whole waves; BYPOS: lane pairs) leave together
+    if ((tid2 >> 1) >= a.ntiles * 32u) // whole tiles (whole waves) leave together
         return;
-    const uint32_t gid = BYPOS ? s.row_of[tid2 >> 1] : tid2 >> 1;
+    const uint32_t gid = tid2 >> 1;
     const uint32_t tile = gid >> 5, row = gid & 31u;
     uint32_t* lrow = rows + ((threadIdx.x >> 1) & 127u) * kDbRowWords;
-    const int p = BYPOS ? (int)(tid2 >> 1) : a.tile_pos[gid];
+    const int p = a.tile_pos[gid];
     uint32_t w[16]; // words 16hh … 16hh + 15 of the row: D4 rows 4hh … 4hh + 3, two cells per word
     int sq = 0;
-    if (p >= 0) {
+    if constexpr (ROWS) {
+        if (p >= 0) {
+            const uint4* pr = reinterpret_cast<const uint4*>(s.pool + (size_t)p * 32 + 16 * hh);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint4 v = pr[k];
+                w[4 * k + 0] = v.x;
+                w[4 * k + 1] = v.y;
+                w[4 * k + 2] = v.z;
+                w[4 * k + 3] = v.w;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                w[k] = 0x02000200u; // padding: b = 0
+        }
+    } else if (p >= 0) {
         const frac_grid_item d = s.doms[s.porig[p]];
         const uint8_t* base = s.src + (size_t)(d.y + 8 * hh) * s.sstride + d.x;
         if ((((uintptr_t)base | s.sstride) & 7u) == 0) {
@@ -452,9 +464,11 @@ __device__ __forceinline__ void dft_domain_build_pair_at(uint32_t tid2, const Mf
 #pragma unroll
     for (int k = 0; k < 16; ++k)
         lrow[16 * hh + k] = w[k];
-    sq += __shfl_xor(sq, 1, 64);
-    if (p >= 0 && hh == 0)
-        s.negsd2[p] = -sq;
+    if constexpr (!ROWS) {
+        sq += __shfl_xor(sq, 1, 64);
+        if (p >= 0 && hh == 0)
+            s.negsd2[p] = -sq;
+    }
     // the pair's LDS writes above are one wave's and precede its reads below in program order
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -509,13 +523,6 @@ __device__ __forceinline__ void dft_domain_build_pair_at(uint32_t tid2, const Mf
         a.dconst[(size_t)tile * (kDftCS * 4) + h * 16 + i] = __float_as_uint(ny);
     }
     uint32_t gx = p >= 0 ? (uint32_t)((F5 ? 2 : 4) * dinf) : 0u, gy = p >= 0 ? (uint32_t)sb2 : 0u;
-    if constexpr (BYPOS) {
-        if (hh == 0) {
-            atomicMax(&tguard[tile].x, gx);
-            atomicMax(&tguard[tile].y, gy);
-        }
-        return;
-    }
     // the tile's guard terms over its 32 rows (lanes 2·row + hh of one wave): a wave maximum
 #pragma unroll
     for (int o = 32; o > 1; o >>= 1) {
@@ -529,11 +536,11 @@ __device__ __forceinline__ void dft_domain_build_pair_at(uint32_t tid2, const Mf
     }
 }
 
-template <bool BYPOS = false, bool F5 = false>
+template <bool F5 = false>
 __global__ void __launch_bounds__(256) dft_domain_build(MfmaDomainPrepArgs a, DftDomainBuildArgs s,
                                                         uint2* __restrict__ tguard, int32_t* __restrict__ trmax = nullptr)
 {
-    dft_domain_build_at<BYPOS, F5>(blockIdx.x * blockDim.x + threadIdx.x, a, s, tguard, trmax);
+    dft_domain_build_at<F5>(blockIdx.x * blockDim.x + threadIdx.x, a, s, tguard, trmax);
 }
 
 // ---------------------------------------------------------------------------
@@ -665,13 +672,23 @@ __device__ __forceinline__ void dft_range_prep_at(uint32_t gid, const MfmaRangeP
 // (T = 8's flipped copies read through the Flip permutation: the same table, another address) and builds that
 // lane half of the fragments and of the orbit-ordered pixel pairs.  Σa² and R6 meet in a lane-pair shuffle;
 // a block's 32 slots are one wave, so its guard stays a wave maximum.
-template <int FORM>
+// RPIX (the SEA tiled form's tp_prep): the range's 64 pixels come from MfmaRangePrepArgs::rpix, the range-order copy
+// the pixel pass stored before the sort (tp_keys): lane h loads its 32-byte half of rpix[ri], no plane row, and the
+// pixel stage is the caller's (lds, 128 slots of kDrRowBytes bytes).
+constexpr uint32_t kDrRowBytes = 68; // LDS bytes per slot: 64 + 4 of padding
+template <int FORM, bool RPIX = false>
 __device__ __forceinline__ void dft_range_prep_pair_at(uint32_t gid2, const MfmaRangePrepArgs& a,
-                                                       uint32_t* __restrict__ rguard)
+                                                       uint32_t* __restrict__ rguard, uint32_t* lds = nullptr)
 {
     constexpr int N = 8, NBF = FORM == 6 ? 6 : FORM == 5 ? 5 : kDftRangeFrags;
-    constexpr uint32_t kRow = 68; // LDS bytes per slot: 64 + 4 of padding
-    __shared__ uint8_t px[128 * kRow];
+    constexpr uint32_t kRow = kDrRowBytes;
+    uint8_t* px;
+    if constexpr (RPIX) {
+        px = reinterpret_cast<uint8_t*>(lds);
+    } else {
+        __shared__ uint8_t own[128 * kRow];
+        px = own;
+    }
     const uint32_t gid = gid2 >> 1, hh = gid2 & 1u;
     if (gid >= a.nblocks * 32u) // whole blocks (whole waves) leave together
         return;
@@ -680,7 +697,16 @@ __device__ __forceinline__ void dft_range_prep_pair_at(uint32_t gid2, const Mfma
     const int ri = a.slot_range[gid];
     uint2 w[4] = {make_uint2(0x80808080u, 0x80808080u), make_uint2(0x80808080u, 0x80808080u),
                   make_uint2(0x80808080u, 0x80808080u), make_uint2(0x80808080u, 0x80808080u)}; // empty: a = 0
-    if (ri >= 0) {
+    if constexpr (RPIX) {
+        if (ri >= 0) {
+            const uint4* q = reinterpret_cast<const uint4*>(a.rpix + (size_t)ri * 64 + 32 * hh);
+            const uint4 v0 = q[0], v1 = q[1];
+            w[0] = make_uint2(v0.x, v0.y);
+            w[1] = make_uint2(v0.z, v0.w);
+            w[2] = make_uint2(v1.x, v1.y);
+            w[3] = make_uint2(v1.z, v1.w);
+        }
+    } else if (ri >= 0) {
         const frac_grid_item rg = a.ranges[ri];
         const uint8_t* base = a.tgt + (size_t)(rg.y + 4 * hh) * a.tstride + rg.x;
         if ((((uintptr_t)base | a.tstride) & 7u) == 0) {

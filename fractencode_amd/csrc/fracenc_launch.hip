@@ -706,7 +706,8 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
     c->form_ran = FRAC_FORM_SEA_MFMA;
     c->flops_ran = 0;
     c->evaluated_ran = 0;
-    // both sides' sort keys, and the run's best_key and fb_count resets (launch_all skipped its fills)
+    // the pixel pass: the pool rows, −ΣD4² and the ranges' pixels (rpix) with both sides' sort keys, and the run's
+    // best_key and fb_count resets (launch_all skipped its fills)
     if (P || nr) {
         TpKeyArgs k;
         k.src = c->d_src.ptr;
@@ -718,7 +719,9 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
         k.nb = (uint32_t)c->bucket_end.size();
         k.dkey = c->d_sea_dkey.ptr;
         k.dpos = c->d_sea_dpos.ptr;
-        k.dblocks = (P + 255) / 256;
+        k.pool = c->d_pool.ptr;
+        k.negsd2 = c->d_negsd2.ptr;
+        k.dblocks = (uint32_t)(((uint64_t)P * 2 + 255) / 256); // two lanes per pool position
         k.tgt = dtgt;
         k.tstride = tstride;
         k.ranges = c->d_ranges.ptr;
@@ -726,9 +729,11 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
         k.nr = nr;
         k.rkey = c->d_sea_rkey.ptr;
         k.rord = c->d_sea_rord.ptr;
+        k.rpix = c->d_tp_rpix.ptr;
         k.best_key = c->d_best_key.ptr;
         k.fb_count = c->d_fb_count.ptr;
-        tp_keys<<<k.dblocks + (nr + 255) / 256, 256, 0, c->stream>>>(k);
+        // two lanes per range
+        tp_keys<<<k.dblocks + (uint32_t)(((uint64_t)nr * 2 + 255) / 256), 256, 0, c->stream>>>(k);
     }
     // Both sides' sorts in the same launches (fracenc_tpsort.hip): stable, tp_key_bits / 8 passes of three small
     // kernels each on this stream, into the tables fill_tp sized.  An even number of passes leaves the sorted
@@ -747,11 +752,6 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
         t.ntiles = nt;
         t.tile_pos = c->d_tp_tile_pos.ptr;
         t.tile_sd = c->d_tp_tile_sd.ptr;
-        t.row_of = c->d_tp_row_of.ptr;
-        t.dtiles = c->d_m_dtiles.ptr;
-        t.dconst = c->d_m_dconst.ptr;
-        t.tguard = c->d_dft_tguard.ptr;
-        t.ks = kTpKS;
         t.tblocks = (nt * 32 + 255) / 256;
         t.rkey = twin ? c->d_sea_rkey2.ptr : c->d_sea_rkey.ptr;
         t.rord = twin ? c->d_sea_rord2.ptr : c->d_sea_rord.ptr;
@@ -762,7 +762,8 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
         t.blk_u = c->d_tp_blk_u.ptr;
         tp_build<<<t.tblocks + (nbk * 32 + 255) / 256, 256, 0, c->stream>>>(t);
     }
-    // the domain tiles by pool position, the range blocks, and the seed work (which reads what tp_build wrote)
+    // the domain tiles from the pool rows, the range blocks from rpix, and the seed work (which reads what
+    // tp_build wrote); the windowed search's guard thresholds come with the tile guards
     const bool search = nr && ng; // else no ranges, or no domain in any range's bucket
     {
         MfmaDomainPrepArgs d;
@@ -780,8 +781,6 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
         b.pool = c->d_pool.ptr;
         b.negsd2 = c->d_negsd2.ptr;
         b.tpool = c->d_dft_tpool.ptr;
-        b.row_of = c->d_tp_row_of.ptr;
-        b.npos = P;
         MfmaRangePrepArgs r;
         r.tgt = dtgt;
         r.tstride = tstride;
@@ -793,6 +792,7 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
         r.rconst = c->d_m_rconst.ptr;
         FRAC_HIP(c, c->d_dft_rorb.ensure((size_t)std::max(nbk, 1u) * 32 * 32));
         r.rorb = c->d_dft_rorb.ptr;
+        r.rpix = c->d_tp_rpix.ptr;
         TpSeedWorkArgs sw;
         if (search) {
             sw.groups = c->d_tp_groups.ptr;
@@ -801,12 +801,12 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
             sw.tile_sd = c->d_tp_tile_sd.ptr;
             sw.work = c->d_tp_work.ptr;
         }
-        const uint64_t dthreads = (uint64_t)P * (kTpPairBuild ? 2 : 1); // lanes per pool position
-        const uint32_t dblocks = nt && P ? (uint32_t)((dthreads + 255) / 256) : 0u;
+        const uint32_t dblocks = (nt * 64 + 255) / 256; // two lanes per tile row, a wave per tile
         const uint32_t rblocks = (nbk * 64 + 255) / 256; // two lanes per range slot
         const uint32_t pg = dblocks + rblocks + (sw.ngroups + 255) / 256;
         if (pg)
-            tp_prep<<<pg, 256, 0, c->stream>>>(d, b, c->d_dft_tguard.ptr, dblocks, r, c->d_dft_rguard.ptr, rblocks, sw);
+            tp_prep<<<pg, 256, 0, c->stream>>>(d, b, c->d_dft_tguard.ptr, kTpFast ? c->d_dft_trmax.ptr : nullptr, dblocks,
+                                               r, c->d_dft_rguard.ptr, rblocks, sw);
     }
     if (timing)
         FRAC_TRY(mark_event(c, 1));
@@ -840,11 +840,6 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
     w.bk = c->tp_bk;
     w.evals = c->d_tp_evals.ptr;
     w.sevals = c->d_tp_sevals.ptr;
-    if (kTpFast) { // the windowed search's guard thresholds, from the tile guards tp_prep finished
-        w.tguard = c->d_dft_tguard.ptr;
-        w.trmax = c->d_dft_trmax.ptr;
-        w.ntiles = nt;
-    }
     tp_seed_windows<<<ng, 256, 0, c->stream>>>(w);
     // the totals (the searched pairs and evaluations) written straight into the host's pinned block
     void* dtot = nullptr;

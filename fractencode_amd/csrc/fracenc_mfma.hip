@@ -266,6 +266,7 @@ struct MfmaRangePrepArgs {
     int fmode = 0;             // mfma_range_prep, the float-C epilogue: B = 8·(128 − copy_t)
     unsigned long long* slotbest = nullptr; // dft_range_prep / mfma_range_prep: [nblocks*32] reset to 0 (the
                                             // searches' merged slot words)
+    const uint8_t* rpix = nullptr; // dft_range_prep_pair_at<…, RPIX>: [nr][64] the ranges' pixels in range order
 };
 
 // the range-block count of a device-planned search (T = 8 Fourier: the originals and their copies)

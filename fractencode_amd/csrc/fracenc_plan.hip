@@ -767,8 +767,8 @@ int fill_tp(frac_ctx* c, const PrepBuckets& B)
     //     fragments, constants and orbit copies (d_m_rfrags, d_m_rconst, d_dft_rorb) and d_m_entries.  dft_prep
     //     writes every row of each, padding rows included, from its own maps (the exhaustive route needs that
     //     frame after frame anyway), so a fallback reads nothing the abandoned attempt laid out.  The pool and
-    //     −ΣD4² are indexed by pool position in both layouts (dft_domain_build<BYPOS> scatters to row_of only
-    //     the tile-order outputs).
+    //     −ΣD4² are indexed by pool position in both layouts (the tiled form writes them in tp_keys, before its
+    //     sort, and reads the rows back by tile; d_tp_rpix, the ranges' pixels in range order, is its own).
     FRAC_HIP(c, c->d_tp_slot_range.ensure(nbk * 32));
     FRAC_HIP(c, c->d_tp_range_slot.ensure(nr));
     FRAC_HIP(c, c->d_tp_tile_pos.ensure(nt * 32));
@@ -785,7 +785,7 @@ int fill_tp(frac_ctx* c, const PrepBuckets& B)
     FRAC_HIP(c, c->d_tp_rec.ensure(nbk * 64));
     FRAC_HIP(c, c->d_tp_sevals.ensure(ng));
     FRAC_HIP(c, c->d_tp_tile_sd.ensure(nt));
-    FRAC_HIP(c, c->d_tp_row_of.ensure(P));
+    FRAC_HIP(c, c->d_tp_rpix.ensure(nr * 64));
     FRAC_HIP(c, c->d_tp_blk_sr.ensure(nbk));
     FRAC_HIP(c, c->d_tp_blk_u.ensure(nbk));
     FRAC_HIP(c, c->h_tp_tot.ensure());

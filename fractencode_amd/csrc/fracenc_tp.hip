@@ -30,13 +30,15 @@
 namespace fracenc {
 
 constexpr int kTpMaxBuckets = 8;
-// tp_prep's domain half: two lanes per pool position (dft_domain_build_pair_at, BYPOS), or one
-// (dft_domain_build_at); DESIGN §7.4 has the two times
-constexpr bool kTpPairBuild = true;
+// The route reads the planes once, in tp_keys, before the sort: the pixel pass forms every pool row
+// (and −ΣD4²) in pool order and copies every range's 64 pixels in range order (rpix), all contiguous stores, with
+// the sort keys from the same registers.  After the sort tp_prep permutes: one whole 128-byte pool row per tile
+// row and one 64-byte rpix row per slot are its only gathers (dft_domain_build_pair_at<…, ROWS>,
+// dft_range_prep_pair_at<…, RPIX>), a tile is one wave, and everything it stores is contiguous per wave.
 // DESIGN §7.10, each measured alone against its absence:
 // kTpFastSearch: the windowed search runs the exhaustive search's tuned variant (the guarded constant-folded
 //   epilogue, the unrolled chunk, wave-uniform buffer_load … lds stages), its per-tile thresholds written by
-//   tp_seed_windows from the guards tp_prep finished; false: the exact epilogue, as the seed search
+//   tp_prep with the tile guards; false: the exact epilogue, as the seed search
 // kTpLongestFirst: the windowed search's workgroups take the groups by window size, longest first (tp_plan's
 //   order); false: in ΣR order, which leaves the longest windows to the middle of the launch
 // (A third, tp_prep storing neither the pool nor −ΣD4² — only the fp32 fallback reads them on this route — took
@@ -52,66 +54,16 @@ struct TpBuckets {
     uint32_t rng_begin[kTpMaxBuckets], rng_count[kTpMaxBuckets];   // sorted ranges
 };
 
-// range sort key: (bucket << 16) | ΣR (ΣR = 4Σr ≤ 65280 < 2^16)
-__device__ __forceinline__ void tp_range_keys_at(uint32_t r, const uint8_t* __restrict__ tgt, uint32_t tstride,
-                                                 const frac_grid_item* __restrict__ ranges,
-                                                 const int32_t* __restrict__ rbucket_idx, uint32_t nr,
-                                                 uint32_t* __restrict__ key, uint32_t* __restrict__ idx)
-{
-    if (r >= nr)
-        return;
-    const frac_grid_item rg = ranges[r];
-    uint32_t s = 0;
-    for (int y = 0; y < 8; ++y)
-#pragma unroll
-        for (int x = 0; x < 8; ++x)
-            s += tgt[(size_t)(rg.y + y) * tstride + rg.x + x];
-    key[r] = ((uint32_t)rbucket_idx[r] << 16) | (4u * s);
-    idx[r] = r;
-}
-
-// domain sort key (bucket << 16) | ΣD4 straight from the plane — ΣD4 is the domain's pixel sum
-// (≤ 256·255 < 2^16) — so the pool is built once, by dft_domain_build, after the sort
 __device__ inline uint32_t byte_sum4(uint32_t w)
 {
     const uint32_t t = (w & 0x00ff00ffu) + ((w >> 8) & 0x00ff00ffu);
     return (t & 0xffffu) + (t >> 16);
 }
 
-__device__ __forceinline__ void tp_domain_keys_at(uint32_t p, const uint8_t* __restrict__ src, uint32_t sstride,
-                                                  const frac_grid_item* __restrict__ doms,
-                                                  const uint32_t* __restrict__ porig, uint32_t P,
-                                                  const uint32_t* __restrict__ bucket_end, uint32_t nb,
-                                                  uint32_t* __restrict__ key, uint32_t* __restrict__ pos)
-{
-    if (p >= P)
-        return;
-    const frac_grid_item d = doms[porig[p]];
-    const uint8_t* base = src + (size_t)d.y * sstride + d.x;
-    uint32_t sd = 0;
-    if ((((uintptr_t)base | sstride) & 7u) == 0) {
-#pragma unroll
-        for (int y = 0; y < 16; ++y) {
-            const uint2* row = reinterpret_cast<const uint2*>(base + (size_t)y * sstride);
-            const uint2 a = row[0], b = row[1];
-            sd += byte_sum4(a.x) + byte_sum4(a.y) + byte_sum4(b.x) + byte_sum4(b.y);
-        }
-    } else {
-        for (int y = 0; y < 16; ++y)
-#pragma unroll
-            for (int x = 0; x < 16; ++x)
-                sd += base[(size_t)y * sstride + x];
-    }
-    uint32_t b = 0;
-    while (b + 1 < nb && p >= bucket_end[b])
-        ++b;
-    key[p] = (b << 16) | sd;
-    pos[p] = p;
-}
-
-// tp_keys: both sides' sort keys and the run's resets in one launch, as dft_prep arranges them.  Blocks
-// [0, dblocks) take the domains, the rest the ranges; every thread also takes a grid-stride share of the
-// best_key reset, and thread 0 clears the fallback count (launch_all leaves both to this kernel).
+// tp_keys: the route's pixel pass, before the sort, in pool and range order — the only kernel of the route that
+// reads the planes — with the run's resets, in one launch as dft_prep arranges them.  Blocks [0, dblocks) take the
+// domains, the rest the ranges; every thread also takes a grid-stride share of the best_key reset, and thread 0
+// clears the fallback count (launch_all leaves both to this kernel).
 struct TpKeyArgs {
     const uint8_t* src;
     uint32_t sstride;
@@ -122,6 +74,8 @@ struct TpKeyArgs {
     uint32_t nb;
     uint32_t* dkey;
     uint32_t* dpos;
+    uint32_t* pool;   // [P][32] packed u16 pairs of D4 (tp_prep's gather; fallback_grid)
+    int32_t* negsd2;  // [P] (fallback_grid)
     uint32_t dblocks; // blocks of the domain half
     const uint8_t* tgt;
     uint32_t tstride;
@@ -130,9 +84,127 @@ struct TpKeyArgs {
     uint32_t nr;
     uint32_t* rkey;
     uint32_t* rord;
+    uint8_t* rpix;    // [nr][64] the ranges' pixels, row-major, in range order (tp_prep's gather)
     unsigned long long* best_key; // nr entries set to ~0 (no candidate yet)
     uint32_t* fb_count;
 };
+
+// Domain half: two lanes per pool position, the first phase of dft_domain_build_pair_at — lane h of a position
+// loads the plane rows of D4 rows 4h … 4h + 3 and forms the 2×2 sums (pair_sums), that half of the pool row.
+// The sort key (bucket << 16) | ΣD4 comes from the same registers: ΣD4, the sum of the row's cells, is the
+// domain's pixel sum (≤ 256·255 < 2^16); so does −ΣD4².  A wave's 32 rows are 4 KiB of the pool, contiguous:
+// staged through LDS, each of its four store instructions covers 1 KiB of whole lines (straight from the
+// registers an instruction would store 16 bytes at a 64-byte stride).
+constexpr uint32_t kTpRowQuads = 9; // LDS uint4 per staged row: 8 + 1 of padding (rows stay 16-byte aligned)
+
+__device__ __forceinline__ void tp_domain_rows_at(uint32_t tid2, const TpKeyArgs& a)
+{
+    __shared__ uint4 rows[128 * kTpRowQuads]; // 256 threads = 128 rows
+    const uint32_t p = tid2 >> 1, hh = tid2 & 1u, lane = threadIdx.x & 63u;
+    const uint32_t p0 = (tid2 - lane) >> 1; // the wave's first position
+    if (p0 >= a.P) // whole waves leave together
+        return;
+    uint32_t w[16] = {}; // words 16hh … 16hh + 15 of the row: D4 rows 4hh … 4hh + 3, two cells per word
+    if (p < a.P) {
+        const frac_grid_item d = a.doms[a.porig[p]];
+        const uint8_t* base = a.src + (size_t)(d.y + 8 * hh) * a.sstride + d.x;
+        if ((((uintptr_t)base | a.sstride) & 7u) == 0) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                // 16 bytes per row: two 8-byte loads (domain origins are 8-byte aligned, not 16)
+                const uint2* r0 = reinterpret_cast<const uint2*>(base + (size_t)(2 * i) * a.sstride);
+                const uint2* r1 = reinterpret_cast<const uint2*>(base + (size_t)(2 * i + 1) * a.sstride);
+                const uint2 a0 = r0[0], a1 = r0[1], b0 = r1[0], b1 = r1[1];
+                w[4 * i + 0] = pair_sums(a0.x, b0.x);
+                w[4 * i + 1] = pair_sums(a0.y, b0.y);
+                w[4 * i + 2] = pair_sums(a1.x, b1.x);
+                w[4 * i + 3] = pair_sums(a1.y, b1.y);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const uint8_t* q = base + (size_t)(2 * (k / 4)) * a.sstride + 4 * (k % 4);
+                const uint32_t w0 = q[0] | (q[1] << 8) | (q[2] << 16) | ((uint32_t)q[3] << 24);
+                const uint8_t* q1 = q + a.sstride;
+                const uint32_t w1 = q1[0] | (q1[1] << 8) | (q1[2] << 16) | ((uint32_t)q1[3] << 24);
+                w[k] = pair_sums(w0, w1);
+            }
+        }
+    }
+    uint32_t sd = 0;
+    int sq = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int lo = (int)(w[k] & 0xffffu), hi = (int)(w[k] >> 16);
+        sd += (uint32_t)(lo + hi);
+        sq += lo * lo + hi * hi;
+    }
+    uint4* lrow = rows + ((threadIdx.x >> 1) & 127u) * kTpRowQuads + 4 * hh;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        lrow[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+    sd += (uint32_t)__shfl_xor((int)sd, 1, 64);
+    sq += __shfl_xor(sq, 1, 64);
+    if (p < a.P && hh == 0) {
+        uint32_t b = 0;
+        while (b + 1 < a.nb && p >= a.bucket_end[b])
+            ++b;
+        a.dkey[p] = (b << 16) | sd;
+        a.dpos[p] = p;
+        a.negsd2[p] = -sq;
+    }
+    // the wave's LDS writes above precede its reads below in program order
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const uint4* wrows = rows + ((threadIdx.x >> 6) & 3u) * 32u * kTpRowQuads;
+    uint4* out = reinterpret_cast<uint4*>(a.pool + (size_t)p0 * 32);
+    const uint32_t nq = min(32u, a.P - p0) * 8u; // the wave's rows in uint4 (the last wave's may be fewer)
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i) {
+        const uint32_t q = i * 64u + lane;
+        if (q < nq)
+            out[q] = wrows[(q >> 3) * kTpRowQuads + (q & 7u)];
+    }
+}
+
+// Range half: two lanes per range, lane h its rows 4h … 4h + 3, as dft_range_prep_pair_at loads them.  The sort
+// key is (bucket << 16) | ΣR (ΣR = 4Σr ≤ 65280 < 2^16); the 64 raw pixels go to rpix[r], row-major, a lane pair's
+// two 16-byte stores each completing a 64-byte row and a wave's rows contiguous.
+__device__ __forceinline__ void tp_range_rows_at(uint32_t gid2, const TpKeyArgs& a)
+{
+    const uint32_t r = gid2 >> 1, hh = gid2 & 1u;
+    if (r >= a.nr) // lane pairs leave together
+        return;
+    const frac_grid_item rg = a.ranges[r];
+    const uint8_t* base = a.tgt + (size_t)(rg.y + 4 * hh) * a.tstride + rg.x;
+    uint2 w[4];
+    if ((((uintptr_t)base | a.tstride) & 7u) == 0) {
+        // one 8-byte load per row (range origins on the 8-pixel grid)
+#pragma unroll
+        for (int y = 0; y < 4; ++y)
+            w[y] = *reinterpret_cast<const uint2*>(base + (size_t)y * a.tstride);
+    } else {
+#pragma unroll
+        for (int y = 0; y < 4; ++y) {
+            const uint8_t* q = base + (size_t)y * a.tstride;
+            w[y] = make_uint2(q[0] | (q[1] << 8) | (q[2] << 16) | ((uint32_t)q[3] << 24),
+                              q[4] | (q[5] << 8) | (q[6] << 16) | ((uint32_t)q[7] << 24));
+        }
+    }
+    uint32_t s = 0;
+#pragma unroll
+    for (int y = 0; y < 4; ++y)
+        s += byte_sum4(w[y].x) + byte_sum4(w[y].y);
+    uint4* out = reinterpret_cast<uint4*>(a.rpix + (size_t)r * 64 + 32 * hh);
+    out[0] = make_uint4(w[0].x, w[0].y, w[1].x, w[1].y);
+    out[1] = make_uint4(w[2].x, w[2].y, w[3].x, w[3].y);
+    s += (uint32_t)__shfl_xor((int)s, 1, 64);
+    if (hh == 0) {
+        a.rkey[r] = ((uint32_t)a.rbucket_idx[r] << 16) | (4u * s);
+        a.rord[r] = r;
+    }
+}
 
 __global__ void __launch_bounds__(256) tp_keys(TpKeyArgs a)
 {
@@ -142,22 +214,17 @@ __global__ void __launch_bounds__(256) tp_keys(TpKeyArgs a)
     if (gt == 0)
         *a.fb_count = 0u;
     if (blockIdx.x < a.dblocks)
-        tp_domain_keys_at(gt, a.src, a.sstride, a.doms, a.porig, a.P, a.bucket_end, a.nb, a.dkey, a.dpos);
+        tp_domain_rows_at(gt, a);
     else
-        tp_range_keys_at((blockIdx.x - a.dblocks) * blockDim.x + threadIdx.x, a.tgt, a.tstride, a.ranges,
-                         a.rbucket_idx, a.nr, a.rkey, a.rord);
+        tp_range_rows_at((blockIdx.x - a.dblocks) * blockDim.x + threadIdx.x, a);
 }
 
-// tile rows from the sorted domain order; per tile [min, max] ΣD4 of its valid rows; for
-// dft_domain_build<BYPOS>: the tile row of each pool position, the padding rows' fragments
-// (b = 0) and epilogue constants, and zeroed tile guards
+// tile rows from the sorted domain order (−1: a padding row, which tp_prep fills as dft_prep does); per tile
+// [min, max] ΣD4 of its valid rows
 __device__ __forceinline__ void tp_build_tiles_at(uint32_t gid, const TpBuckets& bk,
                                                   const uint32_t* __restrict__ skey,
                                                   const uint32_t* __restrict__ spos, uint32_t ntiles,
-                                                  int32_t* __restrict__ tile_pos, uint2* __restrict__ tile_sd,
-                                                  uint32_t* __restrict__ row_of, uint4* __restrict__ dtiles,
-                                                  uint32_t* __restrict__ dconst, uint2* __restrict__ tguard,
-                                                  uint32_t ks)
+                                                  int32_t* __restrict__ tile_pos, uint2* __restrict__ tile_sd)
 {
     if (gid >= ntiles * 32u)
         return;
@@ -169,18 +236,6 @@ __device__ __forceinline__ void tp_build_tiles_at(uint32_t gid, const TpBuckets&
     const bool valid = k < bk.dom_count[b];
     const uint32_t p = valid ? spos[bk.dom_begin[b] + k] : 0u;
     tile_pos[gid] = valid ? (int32_t)p : -1;
-    if (valid) {
-        row_of[p] = gid;
-    } else {
-        for (uint32_t st = 0; st < ks; ++st) // ks fragments per tile (the Fourier form's layout)
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-                dtiles[((size_t)tile * ks + st) * 64 + row + 32 * h] = make_uint4(0u, 0u, 0u, 0u);
-        const uint32_t hh = (row >> 2) & 1u, i = (row & 3u) + 4u * (row >> 3);
-        dconst[(size_t)tile * (kDftCS * 4) + hh * 16 + i] = __float_as_uint(kDftPadY);
-    }
-    if (row == 0)
-        tguard[tile] = make_uint2(0u, 0u);
     if (row == 0) {
         const uint32_t last = min(k + 31u, bk.dom_count[b] - 1u);
         tile_sd[tile] = valid ? make_uint2(skey[bk.dom_begin[b] + k] & 0xffffu,
@@ -224,11 +279,6 @@ struct TpBuildArgs {
     uint32_t ntiles;
     int32_t* tile_pos;
     uint2* tile_sd;
-    uint32_t* row_of;
-    uint4* dtiles;
-    uint32_t* dconst;
-    uint2* tguard;
-    uint32_t ks;
     uint32_t tblocks;     // blocks of the tile half
     const uint32_t* rkey; // sorted range keys and indices
     const uint32_t* rord;
@@ -242,8 +292,7 @@ struct TpBuildArgs {
 __global__ void __launch_bounds__(256) tp_build(TpBuildArgs a)
 {
     if (blockIdx.x < a.tblocks)
-        tp_build_tiles_at(blockIdx.x * blockDim.x + threadIdx.x, a.bk, a.skey, a.spos, a.ntiles, a.tile_pos, a.tile_sd,
-                          a.row_of, a.dtiles, a.dconst, a.tguard, a.ks);
+        tp_build_tiles_at(blockIdx.x * blockDim.x + threadIdx.x, a.bk, a.skey, a.spos, a.ntiles, a.tile_pos, a.tile_sd);
     else
         tp_build_slots_at((blockIdx.x - a.tblocks) * blockDim.x + threadIdx.x, a.bk, a.rkey, a.rord, a.nblocks,
                           a.slot_range, a.range_slot, a.blk_sr, a.blk_u);
@@ -271,8 +320,12 @@ __device__ __forceinline__ void tp_seed_work_at(uint32_t gi, const uint4* __rest
 }
 
 // tp_prep: everything the seed search reads, in one launch after tp_build.  Blocks [0, dblocks) build the domain
-// tiles by pool position (dft_domain_build, BYPOS), the next rblocks the range blocks, two lanes per slot
-// (dft_range_prep_pair_at), and the trailing blocks the seed work, which reads only what tp_build wrote.
+// tiles, one wave per tile and two lanes per tile row, from the pool rows tp_keys wrote (dft_domain_build_pair_at,
+// ROWS): fragments, constants, the tile-order pool copy, the padding rows, and — a wave reduction — the tile's
+// guard terms and its fast-epilogue threshold trmax[tile] (null: not written).  The four entries of padding after
+// trmax[ntiles], which a chunk's one scalar load may touch, are written here too, by the first workgroup.  The next
+// rblocks build the range blocks, two lanes per slot, from rpix (dft_range_prep_pair_at, RPIX), and the trailing
+// blocks the seed work, which reads only what tp_build wrote.
 struct TpSeedWorkArgs {
     const uint4* groups = nullptr;
     uint32_t ngroups = 0; // 0: no seed work in this launch
@@ -282,16 +335,20 @@ struct TpSeedWorkArgs {
 };
 
 __global__ void __launch_bounds__(256) tp_prep(MfmaDomainPrepArgs d, DftDomainBuildArgs s, uint2* __restrict__ tguard,
-                                               uint32_t dblocks, MfmaRangePrepArgs r, uint32_t* __restrict__ rguard,
-                                               uint32_t rblocks, TpSeedWorkArgs w)
+                                               int32_t* __restrict__ trmax, uint32_t dblocks, MfmaRangePrepArgs r,
+                                               uint32_t* __restrict__ rguard, uint32_t rblocks, TpSeedWorkArgs w)
 {
+    // one stage for whichever half the workgroup runs (the domain rows are the larger)
+    static_assert(128 * kDbRowWords * 4 >= 128 * kDrRowBytes, "the range half's pixels fit the domain half's rows");
+    __shared__ uint32_t stage[128 * kDbRowWords];
     if (blockIdx.x < dblocks) {
-        if constexpr (kTpPairBuild)
-            dft_domain_build_pair_at<kDftTpForm != 4, true>(blockIdx.x * blockDim.x + threadIdx.x, d, s, tguard, nullptr);
-        else
-            dft_domain_build_at<true, kDftTpForm != 4>(blockIdx.x * blockDim.x + threadIdx.x, d, s, tguard, nullptr);
+        if (trmax && blockIdx.x == 0 && threadIdx.x < 4u)
+            trmax[d.ntiles + threadIdx.x] = -1; // (padding: masked out by dft_guard_bits)
+        dft_domain_build_pair_at<kDftTpForm != 4, true>(blockIdx.x * blockDim.x + threadIdx.x, d, s, tguard, trmax,
+                                                        stage);
     } else if (blockIdx.x < dblocks + rblocks) {
-        dft_range_prep_pair_at<kDftTpForm>((blockIdx.x - dblocks) * blockDim.x + threadIdx.x, r, rguard);
+        dft_range_prep_pair_at<kDftTpForm, true>((blockIdx.x - dblocks) * blockDim.x + threadIdx.x, r, rguard,
+                                                         stage);
     } else {
         tp_seed_work_at((blockIdx.x - dblocks - rblocks) * blockDim.x + threadIdx.x, w.groups, w.ngroups, w.blk_sr,
                         w.tile_sd, w.work);
@@ -337,11 +394,6 @@ struct TpWindowArgs {
     TpBuckets bk;
     unsigned long long* evals; // [ngroups] (range, domain) pairs in the window (frac_stats.evaluated_mappings)
     unsigned long long* sevals; // [ngroups] (range, domain) pairs of the seed tile, read from work (tp_prep)
-    // kTpFastSearch: the fast epilogue's per-tile thresholds (DftArgs::trmax) from the tiles' finished guards, with
-    // the four entries of padding a chunk's one scalar load may touch; null: not written
-    const uint2* tguard = nullptr;
-    int32_t* trmax = nullptr;
-    uint32_t ntiles = 0;
 };
 
 // one group's window from its blocks' seed bounds (su), with the sums the totals are made of; one thread
@@ -395,20 +447,9 @@ __device__ __forceinline__ void tp_seed_window_at(const TpWindowArgs& a, uint32_
 
 // tp_seed_windows: one workgroup per group.  Each 32-lane row reduces the seed search's records of one block of
 // the group to its bound (tp_seed_reduce_row) and writes blk_u; one thread then sets the group's window.
-// The grid also shares out the windowed search's guard thresholds (TpWindowArgs::trmax): tp_prep raised the tile
-// guards with atomics, so they are final only now, and the seed search (exact epilogue) did not need them.
 __global__ void __launch_bounds__(256) tp_seed_windows(TpWindowArgs a)
 {
     __shared__ uint32_t su[kDftBlocksPerWG];
-    if (a.trmax)
-        for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < a.ntiles + 4u; t += gridDim.x * blockDim.x) {
-            int32_t v = -1; // (padding: masked out by dft_guard_bits)
-            if (t < a.ntiles) {
-                const uint2 g = a.tguard[t];
-                v = dft_fast6_rmax(g.x, g.y);
-            }
-            a.trmax[t] = v;
-        }
     const uint32_t gi = blockIdx.x;
     const uint4 gr = a.groups[gi];
     {
