@@ -1105,7 +1105,7 @@ struct QtPlanArgs {
     uint32_t mfma_per_pair;  // MFMA 32x32x16 per (range block, domain tile) pair: flops accounting
     uint32_t nwork_cap, nent_cap, nblocks_cap, ntiles_cap; // buffer capacities
     uint4* work;
-    uint32_t* blk_ptr;       // [nblocks·copies + 1]
+    uint32_t* blk_ptr;       // [nblocks·copies + 1]; null (with blk_ent): no CSR map (the Fourier levels)
     uint32_t* blk_ent;
     unsigned long long* acc; // frame counters: [5] total mappings, [6] eligible pairs, [7] flops, [8] overflow
     QtFillArgs fill;         // the per-item maps, filled by the same launch (from the header in LDS)
@@ -1238,7 +1238,7 @@ __global__ void __launch_bounds__(256) qt_plan(QtPlanArgs a)
     }
     // the CSR map: block (copy, bucket, k) holds one entry per split of its bucket
     const uint32_t nbt = h.nblocks * a.copies;
-    for (uint32_t i = gt; i <= nbt; i += gs) {
+    for (uint32_t i = gt; a.blk_ptr && i <= nbt; i += gs) {
         if (i == nbt) {
             a.blk_ptr[i] = h.nent;
             continue;

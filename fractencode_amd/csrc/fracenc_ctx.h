@@ -193,16 +193,15 @@ struct frac_ctx {
     uint32_t nblocks = 0, ntiles = 0;
     std::vector<uint4> m_work;             // per WG (4 range blocks: search_mfma)
     std::vector<uint32_t> m_blk_ptr, m_blk_ent;
-    std::vector<uint4> m8_work;            // per WG (8 range blocks: search_dft; m8_bpw for the 16-wave forms)
-    uint32_t m8_bpw = 8;                   // range blocks per workgroup of m8_work
+    std::vector<uint4> m8_work;            // per WG (kDftBlocksPerWG = 8 range blocks: search_dft); no CSR map:
+                                           // the Fourier search merges its splits per slot (d_dft_slotbest)
+    bool m8_built = false;                 // m8_work was built for this geometry (it may still hold no work)
     // T = 8 on the Fourier path (n = 8, ratio 2): Flip_Rotate_k = Flip ∘ Rotate_k (image/transform.h:32-41),
     // so the flip half is the rotation search of each range read through Flip — a second copy of every
     // range block (blocks nblocks .. 2·nblocks − 1, same bucket), resolved together with the original
     // (resolve_dft: Rotate-group index t' of the flipped copy = transform 4 + (−t' mod 4))
     uint32_t dft_copies = 1;
-    std::vector<uint32_t> m8_blk_ptr, m8_blk_ent;
     DBuf<uint4> d_m8_work;
-    DBuf<uint32_t> d_m8_blk_ptr, d_m8_blk_ent;
     DBuf<int32_t> d_m_slot_range, d_m_tile_pos;
     DBuf<uint32_t> d_m_range_slot, d_m_blk_ptr, d_m_blk_ent, d_m_rconst, d_m_dconst;
     DBuf<uint4> d_m_work, d_m_dtiles, d_m_rfrags;
@@ -250,7 +249,7 @@ struct frac_ctx {
     };
     Pinned<TpTotals> h_tp_tot; // mapped: tp_plan writes the run's totals there (read after launch_tp's synchronisation)
     // the tiled form's own maps and work lists, in its sorted layout (rebuilt every run): under AUTO the
-    // MFMA engine's domain-ordered ones (d_m_tile_pos, the slot maps, d_m8_*) stay prepared beside them
+    // MFMA engine's domain-ordered ones (d_m_tile_pos, the slot maps, d_m8_work) stay prepared beside them
     DBuf<int32_t> d_tp_slot_range, d_tp_tile_pos;
     DBuf<uint32_t> d_tp_range_slot;
     DBuf<uint4> d_tp_work;

@@ -14,42 +14,57 @@
 //   2Z_0 = U + Pr,  2Z_2 = U − Pr,  2Z_1 = U' − Pi,  2Z_3 = U' + Pi
 //
 // so  2·max_t Z_t = max(U + |Pr|, U' + |Pi|)  and, with S16 = Σ(4r − D4)² = 16Σa² − 8Z + Σb²,
-// the chunk statistic tracked per lane is the maximum over domains of
+// the statistic whose maximum over domains the search wants is
 //
-//   y = 8·max_t Z_t − Σb²  =  16Σa² − min_t S16                      (one GEMM per tile)
+//   y = 8·max_t Z_t − Σb²  =  16Σa² − min_t S16.
 //
-// Forms (the tile functions below; the default is the six-MFMA form, kDft6, dft_tile_max6):
-//   8-MFMA form  U, U', Pr, Pi as K = 32 GEMMs (8 MFMA 32x32x16 per 32 domains × 32 ranges);
-//   five-MFMA    the DFT's real bins P = U + U', M = U − U' (K = 16 each) and the complex bin by
-//                Gauss's three products, P ± M on the VALU (kDft5);
-//   six-MFMA     the same with M accumulated onto P inside the MFMA (2U, 2U'): 6 MFMA and the
-//                exact epilogue's 4.5 VALU per (range, domain) — against the direct form's
-//                T·n²/16 = 16 MFMA and 4 transforms × 1.5 VALU.
-// Their operand bounds are stated with kDft5 / kDft6; the 8-MFMA form's follow.
+// The six-MFMA form (the only one: 6 MFMA 32x32x16 per 32 domains × 32 ranges, against the direct
+// form's T·n²/16 = 16).  The DFT has two real bins and one complex bin.  The real bins are
+//   P = Σ(s_a + u_a)(s_b + u_b) = U + U',   M = Σ(s_a − u_a)(s_b − u_b) = U − U'      (K = 16 each)
+// and M is accumulated onto P inside the MFMA, once with +(s_a − u_a) and once with −(s_a − u_a):
+// 2U = P + M and 2U' = P − M cost no VALU.  The complex bin Pr + iPi = Σ(α + iβ)(γ − iδ) takes
+// Gauss's three products, the last two accumulated onto the first inside the MFMA:
+//   k1 = Σγ(α + β),   Pr = k1 + Σ(γ − δ)(−β),   Pi = k1 + Σ(−δ − γ)α,
+// with the range operands doubled, so the accumulators hold 2Pr and 2Pi.  Fragments (K = 16 orbits):
+//   domain tile   [s_b + u_b | s_b − u_b | γ | γ − δ | −δ − γ]                          (kDftKS = 5)
+//   range block   [s_a + u_a | s_a − u_a | u_a − s_a | 2(α + β) | −2β | 2α]             (kDftNBF = 6)
+// The search tracks h = y/2 = 4·max_t Z_t − Σb²/2 per lane: the tile's row constant is −Σb²/2 — exact
+// in f32 (Σb² ≤ 2^24, so a half-integer of magnitude ≤ 2^23) —
+//   h = max(2U + |2Pr|, 2U' + |2Pi|) − Σb²/2                      (dft_tile_max6, 4.5 VALU a candidate)
+// and what leaves the search is y = 2h (a power-of-two scale: exact).
 //
-// Exactness of the 8-MFMA form (f16 operands, f32 accumulate, all values integers):
-//   operands  |s_a|,|u_a| ≤ 256, |4s_a| ≤ 1024, |α|,|β| ≤ 255; |s_b|,|u_b| ≤ 1024,
-//             |γ|,|δ| ≤ 1020 — integers of magnitude ≤ 2048 are exact in f16;
-//   products  every partial sum of U, U' (32 terms ≤ 2^18) and Pr, Pi (32 terms ≤ 2^18) is
-//             an integer of magnitude ≤ 2^23: exact in any accumulation order.
-//   fast path (per (range block, domain tile) guard 4·max R1·max D∞ + max Σb² ≤ 2^24, with
-//             R1 = Σ_o(|s_a| + |u_a|) and D∞ = max_o(|s_b|, |u_b|); ≈93 % of tile pairs on S1):
-//             the MFMA starts from C = −Σb² and accumulates 4U (range operands ×4), every
-//             partial sum bounded by the guard, so Ũ = 4U − Σb² is exact; then
-//             y = max(fma(|Pr|, 4, Ũ), fma(|Pi|, 4, Ũ'))  — 2 fma + a shared v_max3.
-//   exact path (guard fails): U, U' from C = 0; 2max Z = max(U + |Pr|, U' + |Pi|) (≤ 2^23,
-//             exact); y = fma(that, 4, −Σb²).
-//   Both:     y is exact whenever |y| ≤ 2^24, which holds for every candidate in the exact
-//             regime S16 < 2^24 (y = 16Σa² − S16, 16Σa² ≤ 2^24).  Candidates with S16 ≥ 2^24
-//             may round, but rounding is monotone: their y ≤ 16Σa² − 2^24 (exactly
-//             representable) stays ≤ it, so they never beat or tie an exact-regime candidate,
-//             and a range whose maximum reaches that bound goes to the fp32 fallback
-//             (App. A.3), as with the direct engine.
-// The per-lane chunk maximum of y and the tile it appeared in feed resolve_dft, which
-// re-derives the exact (domain, transform) inside the chunk with integer arithmetic.
-// resolve_dft reads, per slot: the exhaustive route's per-work-item entries through the block → entry CSR map
-// (SORTED = false), or the search's own merge (slotbest), or, on the SEA tiled form (SORTED = true), the two
-// records search_dft<…, CHUNKED> left for the slot's row halves — no map and no walk over chunks.
+// Exactness (f16 operands, f32 accumulate; a ∈ [−128, 127], b ∈ [−512, 508]; every value an integer):
+//   operands  |s_b ± u_b|, |γ − δ|, |δ + γ| ≤ 2048, |γ| ≤ 1020;  |s_a ± u_a| ≤ 512, |2(α + β)| ≤ 1020,
+//             |2α|, |2β| ≤ 510 — integers of magnitude ≤ 2048 are exact in f16;
+//   2U, 2U'   with A0 = s_a + u_a, A2 = s_a − u_a (B0, B2 on the domain side), |A0| + |A2| =
+//             2·max(|s_a|, |u_a|) ≤ 512 and |B0|, |B2| ≤ 2048: every partial sum of P ± M, in any
+//             accumulation order, is bounded by Σ_o(|A0·B0| + |A2·B2|) ≤ 16·512·2048 = 2^24: exact;
+//   2Pr, 2Pi  partial sums ≤ 2·(16·510·1020 + 16·255·2040) = 33,292,800 < 2^25, all even: exact;
+//   2U + |2Pr| = 4·max(Z_0, Z_2) and 2U' + |2Pi| = 4·max(Z_1, Z_3), of magnitude ≤ 2^24: exact;
+//   h         one rounding of exact operands, exact whenever |y| ≤ 2^24, which holds for every candidate in
+//             the exact regime S16 < 2^24 (y = 16Σa² − S16, 16Σa² ≤ 2^24).  Candidates with S16 ≥ 2^24
+//             may round, but rounding is monotone: their y ≤ 16Σa² − 2^24 (exactly representable) stays
+//             ≤ it, so they never beat or tie an exact-regime candidate, and a range whose maximum reaches
+//             that bound goes to the fp32 fallback (App. A.3), as with the direct engine.
+// The guarded fast path (kDftFast6, dft_tile_max6g) starts the P GEMM from C = −Σb²/2, so both
+// accumulators built on P carry the constant: u' = 2U − Σb²/2, v' = 2U' − Σb²/2, and
+//   h = max(u' + |2Pr|, v' + |2Pi|)              — 2 v_add + 1 v_max3 per candidate instead of 4.5 VALU.
+// Every partial sum of u', v' (C included, any accumulation order) is a half-integer of magnitude
+// ≤ Σb²/2 + Σ_o(|A0||B0| + |A2||B2|) ≤ Σb²/2 + R6·D6, with R6 = Σ_o(|s_a + u_a| + |s_a − u_a|) per range
+// and D6 = max_o max(|s_b + u_b|, |s_b − u_b|) per domain; f32 holds every half-integer below 2^23, so
+// the partial sums are exact whenever
+//   2·R6·D6 + Σb² < 2^24.
+// The guard is taken per (range block, domain tile) from the block's max R6 (rguard) and the tile's max 2·D6
+// and max Σb² (tguard, folded into one threshold on R6: trmax); a tile pair that fails it runs the exact
+// epilogue.  2Pr, 2Pi are exact as above, and u' + |2Pr| = 4·max(Z_0, Z_2) − Σb²/2 is one rounding of exact
+// operands — the argument for h (exact in the exact regime, monotone beyond it) holds unchanged.
+// An 8-MFMA form (U, U', Pr, Pi as K = 32 GEMMs) and a five-MFMA form (P ± M on the VALU) preceded this one;
+// they were measured in DESIGN §7.2 and profiles/r01 – r03 and are gone from the sources.
+//
+// The per-lane maximum of y and the chunk (4 tiles) it appeared in feed resolve_dft, which re-derives the exact
+// (domain, transform) inside the chunk with integer arithmetic.  resolve_dft reads, per slot: the search's own
+// merge over its work items (slotbest; the exhaustive route, SORTED = false) or, on the SEA tiled form
+// (SORTED = true), the two records search_dft<…, CHUNKED> left for the slot's row halves.
 #include "fracenc_common.h"
 
 namespace fracenc {
@@ -122,53 +137,31 @@ constexpr bool flips_valid()
 static_assert(flips_valid<8>(), "the flip half of T = 8 is the rotation search of the flipped range");
 constexpr Orbits4<8> kOrb8 = make_orbits4<8>();
 constexpr float kDftPadY = -1.0e30f; // −Σb² of padding rows: y ≈ −1e30 never wins
-constexpr int kDftRangeFrags = 7;     // s, u, 4s, 4u, α, β, −α
-
-// VAR bit of search_dft: the five-MFMA form (DC / Nyquist bins + a three-product complex bin).
-// The length-4 DFT of the per-orbit correlation has two real bins and one complex bin, so with
-// P = Σ(s_a + u_a)(s_b + u_b) = U + U' and M = Σ(s_a − u_a)(s_b − u_b) = U − U' (one K = 16
-// GEMM each) and the complex bin Pr + iPi = Σ(α + iβ)(γ − iδ) by Gauss's three products
-//   k1 = Σγ(α + β),  Pr = k1 + Σ(γ − δ)(−β),  Pi = k1 + Σ(−δ − γ)α
-// (the last two accumulate onto k1 inside the MFMA), a tile pair costs 5 MFMA 32x32x16
-// instead of 8.  The range operands of the complex bin are doubled so that
-//   y = fma(max(P + M + |2Pr|, P − M + |2Pi|), 2, −Σb²)   (= 4·max(U + |Pr|, U' + |Pi|) − Σb²).
-// Exactness (a ∈ [−128, 127], b ∈ [−512, 508]; every value an integer):
-//   operands  |s_b ± u_b|, |γ − δ|, |δ + γ| ≤ 2048, |γ| ≤ 1020; |s_a ± u_a| ≤ 512,
-//             |2(α + β)| ≤ 1020, |2α|, |2β| ≤ 510: exact in f16;
-//   P         partial sums ≤ 16·512·2048 = 2^24; M ≤ 16·510·2040 < 2^24: exact;
-//   2Pr, 2Pi  partial sums ≤ 2·(16·510·1020 + 16·255·2040) = 33,292,800 < 2^25, all even: exact;
-//   P ± M     = 2U, 2U' (|·| ≤ 2^24): exact; + |2Pr| = 4·max(Z_0, Z_2) (≤ 2^24): exact;
-//   y         one rounding, exact whenever |y| ≤ 2^24 — the exact-form argument below.
-constexpr int kDft5 = 2048;
-constexpr int kDftScalar = 4096; // with kDft5: the P ± M and the fma one row per instruction
-constexpr int kDft6 = 8192;      // the six-MFMA form (dft_tile_max6)
-constexpr int kDftFast6 = 16384; // with kDft6: the guarded constant-folded epilogue (dft_tile_max6_fast)
-// issue-cost knobs of the search loop (A/B): the 4-tile chunk unrolled (LDS reads at immediate
-// offsets from one base), the stage's LDS-DMA by buffer_load … lds (the stage base in an SGPR
-// soffset, per-thread offsets fixed: no VALU per piece), waves of the second half at s_setprio 1
+constexpr int kDftKS = 5;  // domain fragments per tile
+constexpr int kDftNBF = 6; // range fragments per block
 // Row constants of a Fourier tile: [2][16] f32 = 8 uint4, padded to kDftCS = 16 uint4 per tile in
 // memory and in the LDS stage, so a 4-tile stage's constants are exactly one 1 KiB LDS-DMA piece
 constexpr uint32_t kDftCS = 16;
-constexpr int kDftUnroll = 32768;
-constexpr int kDftBufDma = 65536;
-constexpr int kDftPrio = 131072;
 
-// The five- and six-MFMA forms track h = y/2 = 4·max_t Z_t − Σb²/2 instead of y: the row constant
-// (dconst) is −Σb²/2 — exact in f32 (Σb² ≤ 2^24, so a half-integer of magnitude ≤ 2^23) — and the
-// epilogue adds it instead of an fma by 2.  The entries keep y (= 2h, exact: a power-of-two scale),
-// so resolve_dft and the SEA tiled form read them unchanged.
-//
-// The guarded fast path of the six-MFMA form (kDftFast6) starts the P GEMM from C = −Σb²/2, so
-// both accumulators built on P carry the constant: u' = 2U − Σb²/2, v' = 2U' − Σb²/2, and
-//   h = max(u' + |2Pr|, v' + |2Pi|)      — 2 v_add + 1 v_max3 per candidate instead of 4.5 VALU.
-// Exactness: every partial sum of u', v' (C included, any accumulation order) is a half-integer of
-// magnitude ≤ Σb²/2 + Σ_o(|A0||B0| + |A2||B2|) ≤ Σb²/2 + R6·D6, with R6 = Σ_o(|s_a + u_a| + |s_a − u_a|)
-// per range and D6 = max_o max(|s_b + u_b|, |s_b − u_b|) per domain; f32 holds every half-integer
-// below 2^23, so the partial sums are exact whenever 2·R6·D6 + Σb² < 2^24.  The guard is taken per
-// (range block, domain tile) from the block's max R6 (rguard) and the tile's max 2·D6 and max Σb²
-// (tguard); a tile pair that fails it runs the exact epilogue.  2Pr, 2Pi are exact as in kDft5, and
-// u' + |2Pr| = 4·max(Z_0, Z_2) − Σb²/2 is one rounding of exact operands — the exact-form argument
-// (exact in the exact regime, monotone beyond it) holds unchanged.
+// The two forms of search_dft, by their variant words.  The words keep the values the profiles of rounds 3 – 20
+// and the tests name them by; of their bits only kDftFast6 still selects anything, and the tuning build's ablation
+// bits (8, 16, 32, 64, 256, 512) are ORed onto them.
+//   kDftExactVar  the exact epilogue, row constants in registers (dft_tile_max6), the chunk as a loop, stages by
+//                 global_load_lds (stage_tiles): the SEA tiled form's seed search, and the A/B of the guard;
+//   kDftFastVar   variant 35, the shipped search: the guarded folded epilogue (dft_tile_max6g), the 4-tile chunk
+//                 unrolled (LDS reads at immediate offsets from one base) and stages by buffer_load … lds (the
+//                 stage base in an SGPR soffset, per-thread offsets fixed: no VALU per piece).
+constexpr int kDftExactVar = 9217;
+constexpr int kDftFast6 = 16384;
+constexpr int kDftFastVar = 123905;
+static_assert((kDftFastVar & kDftFast6) != 0 && (kDftExactVar & kDftFast6) == 0 &&
+                  ((kDftFastVar | kDftExactVar) & (8 | 16 | 32 | 64 | 256 | 512)) == 0,
+              "the variant words");
+template <int VAR>
+struct DftForm {
+    static constexpr bool FAST6 = (VAR & kDftFast6) != 0;
+};
+
 constexpr int64_t kFast6Limit = (1ll << 24) - 1; // 2·R6·D6 + Σb² ≤ this
 // the guard of a tile with guard terms {gx = max 2·D6, gy = max Σb²} as one threshold on the block's R6:
 // R6·gx + gy ≤ kFast6Limit  ⇔  gy ≤ kFast6Limit and R6 ≤ ⌊(kFast6Limit − gy) / gx⌋  (−1: no block passes)
@@ -179,25 +172,9 @@ __device__ inline int32_t dft_fast6_rmax(uint32_t gx, uint32_t gy)
                                       : (int32_t)min<int64_t>((kFast6Limit - gy) / gx, INT32_MAX);
 }
 
-// the form the SEA engine's tiled search (fracenc_tp.hip) runs: 4 or 6
-constexpr int kDftTpForm = 6;
-
-template <int VAR>
-struct DftForm {
-    static constexpr bool F5 = (VAR & kDft5) != 0;
-    static constexpr bool F6 = (VAR & kDft6) != 0;
-    static constexpr bool FAST6 = F6 && (VAR & kDftFast6) != 0;
-    static constexpr bool HALF = F5 || F6;                        // tracks h = y/2 (row constant −Σb²/2)
-    static constexpr int KS = (F5 || F6) ? 5 : 4;                 // domain fragments per tile
-    static constexpr int NBF = F6 ? 6 : F5 ? 5 : kDftRangeFrags; // range fragments per block
-};
-
 struct DftArgs {
     MfmaSearchArgs m;
-    uint32_t* rguard;     // [nblocks]  max over the block's ranges of R1 = Σ_o(|s_a| + |u_a|) (six-MFMA
-                          //            form: R6 = Σ_o(|s_a + u_a| + |s_a − u_a|))
-    uint2* tguard;        // [ntiles]   {max 4·D∞, max Σb²} over the tile's valid rows (five- / six-MFMA
-                          //            layout: {max 2·D6, max Σb²})
+    uint32_t* rguard;      // [nblocks]  max over the block's ranges of R6 = Σ_o(|s_a + u_a| + |s_a − u_a|)
     uint4* rec = nullptr;  // CHUNKED: [nblocks·64] per block and lane the window's maximum and the chunks attaining
                            // it, {bits of max y (+inf = hit), n chunks attaining it, the first's word, the second's}
                            // with a chunk's word tile | tile mask << 28 (fracenc_tp.hip)
@@ -207,10 +184,10 @@ struct DftArgs {
                                      // index) — the windows longest first (tp_plan, fracenc_tp.hip)
     unsigned long long* stamps = nullptr; // FRAC_CLOCK_STAMP builds only: [workgroups][kClockStampWords]
     // not CHUNKED: per range slot the maximum over every work item, merged here with one 64-bit atomicMax per
-    // (slot, work item) instead of per-work-item entries: fmap(y) << 32 | (kSlotBestTileMax − chunk) << 6 |
-    // the chunk's tiles to re-evaluate << 2 | the lane halves of that chunk attaining y.  The greatest word names
-    // the greatest y and, among equal y, the earliest chunk — the chunk resolve_dft walked the entries for.  The
-    // tile mask is 0xf unless the search tracked the tiles attaining y (TMASK); 0 = no work item reached the slot.
+    // (slot, work item): fmap(y) << 32 | (kSlotBestTileMax − chunk) << 6 | the chunk's tiles to re-evaluate << 2 |
+    // the lane halves of that chunk attaining y.  The greatest word names the greatest y and, among equal y, the
+    // earliest chunk.  The tile mask is 0xf unless the search tracked the tiles attaining y (TMASK); 0 = no work
+    // item reached the slot.
     unsigned long long* slotbest = nullptr;
 };
 constexpr uint32_t kSlotBestTileMax = 0x3ffffffu; // chunk tiles below 2^26 (domains < 2^24: tiles < 2^19)
@@ -219,18 +196,15 @@ constexpr uint32_t kSlotBestTileMax = 0x3ffffffu; // chunk tiles below 2^26 (dom
 constexpr uint32_t kClockStampWords = 6;
 
 // ---------------------------------------------------------------------------
-// dft_domain_build: pool_build + dft_domain_prep in one pass for the Fourier path.  One
-// thread per (tile, row) = per pool position: the 2×2 sums come straight from the plane
-// (SamplerBilinear's integer sum, image/sampler.h:21-38, as pool_build), two cells per
-// 32-bit word — (w & 0x00ff00ff) + ((w >> 8) & 0x00ff00ff) over the word of both rows is
-// the packed u16 pair the pool stores — and the same registers feed the tile fragments.
+// The domain half of the preparation: pool_build and the tile fragments in one pass.  The 2×2 sums come straight
+// from the plane (SamplerBilinear's integer sum, image/sampler.h:21-38, as pool_build), two cells per 32-bit
+// word — (w & 0x00ff00ff) + ((w >> 8) & 0x00ff00ff) over the word of both rows is the packed u16 pair the pool
+// stores — and the same registers feed the tile fragments.
 // Outputs: the pool and −ΣD4² (read by fit_winner and fallback_grid; on the tiled form's route, whose fit is
 // fused into its resolve, only by fallback_grid — not storing them there measured too little: DESIGN §7.10), the
-// pool rows again in
-// tile order (resolve_dft); per 32-domain tile the A fragments of the four K-steps
-// [s_b | u_b | γ | δ] (lane l: row l&31, orbit 8(l>>5) + j), −Σb² per row in the [2][16]
-// lane-half layout of the epilogue, and the tile's fast-path guard terms.  Every pool
-// position sits in exactly one tile row.
+// pool rows again in tile order, orbit order (resolve_dft); per 32-domain tile the kDftKS A fragments (lane l:
+// row l&31, orbit 8(l>>5) + j), −Σb²/2 per row in the [2][16] lane-half layout of the epilogue, and the tile's
+// guard terms {max 2·D6, max Σb²} with their threshold on R6.  Every pool position sits in exactly one tile row.
 // ---------------------------------------------------------------------------
 struct DftDomainBuildArgs {
     const uint8_t* src;
@@ -244,153 +218,26 @@ struct DftDomainBuildArgs {
 
 // pair_sums: fracenc_kernels.hip (pool_build)
 
-// F5: the five-MFMA form's fragments [s_b + u_b | s_b − u_b | γ | γ − δ | −δ − γ] (kDft5)
-template <bool F5 = false>
-__device__ __forceinline__ void dft_domain_build_at(uint32_t tid, const MfmaDomainPrepArgs& a, const DftDomainBuildArgs& s,
-                                                    uint2* __restrict__ tguard, int32_t* __restrict__ trmax)
-{
-    constexpr int NN = 64, NO = 16, KS = F5 ? 5 : 4;
-    if (tid >= a.ntiles * 32u)
-        return;
-    const uint32_t gid = tid;
-    const uint32_t tile = gid >> 5, row = gid & 31u;
-    const int p = a.tile_pos[gid];
-    uint32_t w[NN / 2];
-    if (p >= 0) {
-        const frac_grid_item d = s.doms[s.porig[p]];
-        const uint8_t* base = s.src + (size_t)d.y * s.sstride + d.x;
-        if ((((uintptr_t)base | s.sstride) & 7u) == 0) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                // 16 bytes per row: two 8-byte loads (domain origins are 8-byte aligned, not 16)
-                const uint2* r0 = reinterpret_cast<const uint2*>(base + (size_t)(2 * i) * s.sstride);
-                const uint2* r1 = reinterpret_cast<const uint2*>(base + (size_t)(2 * i + 1) * s.sstride);
-                const uint2 a0 = r0[0], a1 = r0[1], b0 = r1[0], b1 = r1[1];
-                w[4 * i + 0] = pair_sums(a0.x, b0.x);
-                w[4 * i + 1] = pair_sums(a0.y, b0.y);
-                w[4 * i + 2] = pair_sums(a1.x, b1.x);
-                w[4 * i + 3] = pair_sums(a1.y, b1.y);
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < NN / 2; ++k) {
-                const uint8_t* q = base + (size_t)(2 * (k / 4)) * s.sstride + 4 * (k % 4);
-                const uint32_t w0 = q[0] | (q[1] << 8) | (q[2] << 16) | ((uint32_t)q[3] << 24);
-                const uint8_t* q1 = q + s.sstride;
-                const uint32_t w1 = q1[0] | (q1[1] << 8) | (q1[2] << 16) | ((uint32_t)q1[3] << 24);
-                w[k] = pair_sums(w0, w1);
-            }
-        }
-        uint4* pw = reinterpret_cast<uint4*>(s.pool + (size_t)p * (NN / 2));
-        int sq = 0;
-#pragma unroll
-        for (int k = 0; k < NN / 2; ++k) {
-            const int lo = (int)(w[k] & 0xffffu), hi = (int)(w[k] >> 16);
-            sq += lo * lo + hi * hi;
-        }
-#pragma unroll
-        for (int k = 0; k < NN / 8; ++k)
-            pw[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
-        // the tile-order copy for resolve_dft, orbit o as (D_{o,0} | D_{o,1} << 16), (D_{o,2} | D_{o,3} << 16)
-        auto cell = [&](int q) { return (w[q >> 1] >> (16 * (q & 1))) & 0xffffu; };
-        uint4* tw = reinterpret_cast<uint4*>(s.tpool + (size_t)gid * (NN / 2));
-#pragma unroll
-        for (int v = 0; v < NN / 8; ++v) {
-            uint32_t d[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int o = 2 * v + (e >> 1), k = 2 * (e & 1);
-                d[e] = cell(kOrb8.p[o][k]) | (cell(kOrb8.p[o][k + 1]) << 16);
-            }
-            tw[v] = make_uint4(d[0], d[1], d[2], d[3]);
-        }
-        s.negsd2[p] = -sq;
-    } else {
-#pragma unroll
-        for (int k = 0; k < NN / 2; ++k)
-            w[k] = 0x02000200u; // padding: b = 0
-    }
-    int b[NN];
-    int sb2 = 0;
-#pragma unroll
-    for (int k = 0; k < NN / 2; ++k) {
-        b[2 * k] = (int)(w[k] & 0xffffu) - 512;
-        b[2 * k + 1] = (int)(w[k] >> 16) - 512;
-    }
-#pragma unroll
-    for (int k = 0; k < NN; ++k)
-        sb2 += b[k] * b[k];
-    _Float16 comp[KS][NO];
-    int dinf = 0;
-#pragma unroll
-    for (int o = 0; o < NO; ++o) {
-        const int b0 = b[kOrb8.p[o][0]], b1 = b[kOrb8.p[o][1]], b2 = b[kOrb8.p[o][2]], b3 = b[kOrb8.p[o][3]];
-        const int sb = b0 + b2, ub = b1 + b3, gb = b0 - b2, db = b1 - b3;
-        // guard term: D∞ = max(|s_b|, |u_b|) (8-MFMA form); D6 = max(|s_b + u_b|, |s_b − u_b|) (F5 layout)
-        dinf = F5 ? max(dinf, max(abs(sb + ub), abs(sb - ub))) : max(dinf, max(abs(sb), abs(ub)));
-        if constexpr (F5) {
-            comp[0][o] = (_Float16)(sb + ub);
-            comp[1][o] = (_Float16)(sb - ub);
-            comp[2][o] = (_Float16)gb;
-            comp[3][o] = (_Float16)(gb - db);
-            comp[4][o] = (_Float16)(-db - gb);
-        } else {
-            comp[0][o] = (_Float16)sb;
-            comp[1][o] = (_Float16)ub;
-            comp[2][o] = (_Float16)gb;
-            comp[3][o] = (_Float16)db;
-        }
-    }
-#pragma unroll
-    for (int st = 0; st < KS; ++st)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            _Float16 v8[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                v8[j] = comp[st][8 * h + j];
-            a.dtiles[((size_t)tile * KS + st) * 64 + row + 32 * h] = __builtin_bit_cast(uint4, v8);
-        }
-    // the row constant: −Σb² (8-MFMA form, tracks y), −Σb²/2 (F5 layout: the five- and six-MFMA
-    // forms track h = y/2; exact, Σb² ≤ 2^24)
-    const float ny = p >= 0 ? (F5 ? -0.5f * (float)sb2 : -(float)sb2) : kDftPadY;
-    const uint32_t h = (row >> 2) & 1u, i = (row & 3u) + 4u * (row >> 3);
-    a.dconst[(size_t)tile * (kDftCS * 4) + h * 16 + i] = __float_as_uint(ny);
-    uint32_t gx = p >= 0 ? (uint32_t)((F5 ? 2 : 4) * dinf) : 0u, gy = p >= 0 ? (uint32_t)sb2 : 0u;
-    // the tile's guard terms over its valid rows: a 32-lane maximum (whole tiles leave together
-    // above), one writer per tile
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) {
-        gx = max(gx, (uint32_t)__shfl_xor((int)gx, o, 64));
-        gy = max(gy, (uint32_t)__shfl_xor((int)gy, o, 64));
-    }
-    if (row == 0) {
-        tguard[tile] = make_uint2(gx, gy);
-        // the six-MFMA fast path's guard as one threshold on the block's R6
-        if (F5 && trmax)
-            trmax[tile] = dft_fast6_rmax(gx, gy);
-    }
-}
 
-// dft_domain_build_at restated with two lanes per tile row (dft_prep, round 4): lane h of a row loads
+// dft_domain_build_pair_at: two lanes per tile row.  Lane h of a row loads
 // the plane rows of D4 rows 4h … 4h + 3, writes that half of the pool row, and puts it in LDS; each lane
 // then reads the cells of orbits 8h … 8h + 7 back (LDS addresses from the orbit table, no register
 // indexing) and builds that lane half of the fragments and of the tile-order copy.  Σb², ΣD4² and the
-// guard terms meet in a lane-pair shuffle.  On a small frame the single-thread chain per row ran one
-// wave per CU on a quarter of the CUs (C2: 16 workgroups); this halves the chain and doubles the waves.
-// A tile's 32 rows are one wave's 64 lanes, so the tile guards stay a wave reduction.
+// guard terms meet in a lane-pair shuffle.  (One thread per row ran, on a small frame, one wave per CU on a
+// quarter of the CUs — C2: 16 workgroups; the pair halves the chain and doubles the waves.)
+// A tile's 32 rows are one wave's 64 lanes, so the tile guards are a wave reduction.
 // ROWS (the SEA tiled form's tp_prep, fracenc_tp.hip): the pool rows and −ΣD4² are already there, written in pool
 // order by the pixel pass before the sort (tp_keys), so the lane pair reads the plane not at all: lane h loads its
 // 64-byte half of pool[p] — p in ΣD4 order, the route's one gather per domain, a whole 128-byte line per pair —
 // and writes neither.  Everything after the load is the same code.  Its row stage is the caller's (lds, 128 rows of
 // kDbRowWords words), which tp_prep shares with its range half.
 constexpr uint32_t kDbRowWords = 33; // LDS words per row: 32 + 1 of padding (rows in distinct banks)
-template <bool F5, bool ROWS = false>
+template <bool ROWS = false>
 __device__ __forceinline__ void dft_domain_build_pair_at(uint32_t tid2, const MfmaDomainPrepArgs& a,
                                                          const DftDomainBuildArgs& s, uint2* __restrict__ tguard,
                                                          int32_t* __restrict__ trmax, uint32_t* lds = nullptr)
 {
-    constexpr int KS = F5 ? 5 : 4;
+    constexpr int KS = kDftKS;
     uint32_t* rows; // 256 threads = 128 rows
     if constexpr (ROWS) {
         rows = lds;
@@ -498,19 +345,12 @@ __device__ __forceinline__ void dft_domain_build_pair_at(uint32_t tid2, const Mf
         const int b0 = cv[j][0] - 512, b1 = cv[j][1] - 512, b2 = cv[j][2] - 512, b3 = cv[j][3] - 512;
         sb2 += b0 * b0 + b1 * b1 + b2 * b2 + b3 * b3;
         const int sb = b0 + b2, ub = b1 + b3, gb = b0 - b2, db = b1 - b3;
-        dinf = F5 ? max(dinf, max(abs(sb + ub), abs(sb - ub))) : max(dinf, max(abs(sb), abs(ub)));
-        if constexpr (F5) {
-            comp[0][j] = (_Float16)(sb + ub);
-            comp[1][j] = (_Float16)(sb - ub);
-            comp[2][j] = (_Float16)gb;
-            comp[3][j] = (_Float16)(gb - db);
-            comp[4][j] = (_Float16)(-db - gb);
-        } else {
-            comp[0][j] = (_Float16)sb;
-            comp[1][j] = (_Float16)ub;
-            comp[2][j] = (_Float16)gb;
-            comp[3][j] = (_Float16)db;
-        }
+        dinf = max(dinf, max(abs(sb + ub), abs(sb - ub))); // guard term D6
+        comp[0][j] = (_Float16)(sb + ub);
+        comp[1][j] = (_Float16)(sb - ub);
+        comp[2][j] = (_Float16)gb;
+        comp[3][j] = (_Float16)(gb - db);
+        comp[4][j] = (_Float16)(-db - gb);
     }
 #pragma unroll
     for (int st = 0; st < KS; ++st)
@@ -518,11 +358,11 @@ __device__ __forceinline__ void dft_domain_build_pair_at(uint32_t tid2, const Mf
     sb2 += __shfl_xor(sb2, 1, 64);
     dinf = max(dinf, __shfl_xor(dinf, 1, 64));
     if (hh == 0) {
-        const float ny = p >= 0 ? (F5 ? -0.5f * (float)sb2 : -(float)sb2) : kDftPadY;
+        const float ny = p >= 0 ? -0.5f * (float)sb2 : kDftPadY; // −Σb²/2: exact (Σb² ≤ 2^24)
         const uint32_t h = (row >> 2) & 1u, i = (row & 3u) + 4u * (row >> 3);
         a.dconst[(size_t)tile * (kDftCS * 4) + h * 16 + i] = __float_as_uint(ny);
     }
-    uint32_t gx = p >= 0 ? (uint32_t)((F5 ? 2 : 4) * dinf) : 0u, gy = p >= 0 ? (uint32_t)sb2 : 0u;
+    uint32_t gx = p >= 0 ? (uint32_t)(2 * dinf) : 0u, gy = p >= 0 ? (uint32_t)sb2 : 0u;
     // the tile's guard terms over its 32 rows (lanes 2·row + hh of one wave): a wave maximum
 #pragma unroll
     for (int o = 32; o > 1; o >>= 1) {
@@ -531,156 +371,32 @@ __device__ __forceinline__ void dft_domain_build_pair_at(uint32_t tid2, const Mf
     }
     if (row == 0 && hh == 0) {
         tguard[tile] = make_uint2(gx, gy);
-        if (F5 && trmax)
+        if (trmax) // the fast path's guard as one threshold on the block's R6
             trmax[tile] = dft_fast6_rmax(gx, gy);
     }
 }
 
-template <bool F5 = false>
-__global__ void __launch_bounds__(256) dft_domain_build(MfmaDomainPrepArgs a, DftDomainBuildArgs s,
-                                                        uint2* __restrict__ tguard, int32_t* __restrict__ trmax = nullptr)
-{
-    dft_domain_build_at<F5>(blockIdx.x * blockDim.x + threadIdx.x, a, s, tguard, trmax);
-}
-
 // ---------------------------------------------------------------------------
-// dft_range_prep: per range block the seven distinct B fragments
-//   f0 = s_a, f1 = u_a, f2 = 4s_a, f3 = 4u_a, f4 = α, f5 = β, f6 = −α
-// (lane l: range slot l&31, orbit 8(l>>5) + j); U = [f0|f1], U' = [f1|f0] (×4: f2, f3),
-// Pr = [f4|f5], Pi = [f5|f6] against the domain K-steps [s_b|u_b], [γ|δ].  Also 16Σa² per
-// slot and the block's guard term max R1.  One thread per slot (a range-order variant with
-// scattered outputs measured slower for the SEA tiled form's ΣR-sorted slots: 61 vs 41 µs).
-// ---------------------------------------------------------------------------
-// FORM 5: the five-MFMA form's fragments [s_a + u_a | s_a − u_a | 2(α + β) | −2β | 2α] (kDft5);
-// FORM 6: the six-MFMA form's [s_a + u_a | s_a − u_a | u_a − s_a | 2(α + β) | −2β | 2α] (kDft6)
-template <int FORM = 4>
-__device__ __forceinline__ void dft_range_prep_at(uint32_t gid, const MfmaRangePrepArgs& a, uint32_t* __restrict__ rguard)
-{
-    constexpr int N = 8, NN = 64, NO = 16, NBF = FORM == 6 ? 6 : FORM == 5 ? 5 : kDftRangeFrags;
-    if (gid >= a.nblocks * 32u)
-        return;
-    const uint32_t b = gid >> 5, col = gid & 31u;
-    const int ri = a.slot_range[gid];
-    int av[NN];
-    int sa2 = 0;
-    if (ri >= 0) {
-        const frac_grid_item rg = a.ranges[ri];
-        const uint8_t* base = a.tgt + (size_t)rg.y * a.tstride + rg.x;
-        if ((((uintptr_t)base | a.tstride) & 7u) == 0) {
-            // one 8-byte load per row (range origins on the 8-pixel grid)
-#pragma unroll
-            for (int y = 0; y < N; ++y) {
-                const uint2 w = *reinterpret_cast<const uint2*>(base + (size_t)y * a.tstride);
-#pragma unroll
-                for (int x = 0; x < N; ++x)
-                    av[y * N + x] = (int)(((x < 4 ? w.x : w.y) >> (8 * (x & 3))) & 0xffu) - 128;
-            }
-        } else {
-#pragma unroll
-            for (int q = 0; q < NN; ++q)
-                av[q] = (int)base[(size_t)(q / N) * a.tstride + (q % N)] - 128;
-        }
-#pragma unroll
-        for (int q = 0; q < NN; ++q)
-            sa2 += av[q] * av[q];
-        if (b >= a.flip_from) {
-            // T = 8: the block's flipped copy, a'(q) = a(Flip q).  Flip_Rotate_k = Flip ∘ Rotate_k
-            // (fwd(4 + k, p) = fwd(4, fwd(k, p)), image/transform.h:32-41) and Flip ∘ g^k ∘ Flip = g^−k, so
-            // Σ_p a(p)·b(fwd(4 + k, p)) = Σ_q a'(q)·b(g^{−k} q): the copy's rotation t' is transform 4 + (−t' mod 4)
-            int fv[NN];
-#pragma unroll
-            for (int q = 0; q < NN; ++q)
-                fv[q] = av[fwd_index<N>(4, q)];
-#pragma unroll
-            for (int q = 0; q < NN; ++q)
-                av[q] = fv[q];
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < NN; ++q)
-            av[q] = 0;
-    }
-    _Float16 comp[NBF][NO];
-    int r1 = 0;
-#pragma unroll
-    for (int o = 0; o < NO; ++o) {
-        const int a0 = av[kOrb8.p[o][0]], a1 = av[kOrb8.p[o][1]], a2 = av[kOrb8.p[o][2]], a3 = av[kOrb8.p[o][3]];
-        const int sa = a0 + a2, ua = a1 + a3, al = a0 - a2, be = a1 - a3;
-        // guard term: R1 = Σ(|s_a| + |u_a|); the six-MFMA form's R6 = Σ(|s_a + u_a| + |s_a − u_a|)
-        r1 += FORM == 6 ? abs(sa + ua) + abs(sa - ua) : abs(sa) + abs(ua);
-        if constexpr (FORM == 5) {
-            comp[0][o] = (_Float16)(sa + ua);
-            comp[1][o] = (_Float16)(sa - ua);
-            comp[2][o] = (_Float16)(2 * (al + be));
-            comp[3][o] = (_Float16)(-2 * be);
-            comp[4][o] = (_Float16)(2 * al);
-        } else if constexpr (FORM == 6) {
-            comp[0][o] = (_Float16)(sa + ua);
-            comp[1][o] = (_Float16)(sa - ua);
-            comp[2][o] = (_Float16)(ua - sa);
-            comp[3][o] = (_Float16)(2 * (al + be));
-            comp[4][o] = (_Float16)(-2 * be);
-            comp[5][o] = (_Float16)(2 * al);
-        } else {
-            comp[0][o] = (_Float16)sa;
-            comp[1][o] = (_Float16)ua;
-            comp[2][o] = (_Float16)(4 * sa);
-            comp[3][o] = (_Float16)(4 * ua);
-            comp[4][o] = (_Float16)al;
-            comp[5][o] = (_Float16)be;
-            comp[6][o] = (_Float16)(-al);
-        }
-    }
-#pragma unroll
-    for (int f = 0; f < NBF; ++f)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            _Float16 v8[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                v8[j] = comp[f][8 * h + j];
-            a.rfrags[((size_t)b * NBF + f) * 64 + col + 32 * h] = __builtin_bit_cast(uint4, v8);
-        }
-    a.rconst[gid] = ri >= 0 ? (uint32_t)(16 * sa2) : 0u; // 16Σa² ≤ 2^24
-    if (a.slotbest)
-        a.slotbest[gid] = 0ull; // the run's reset of the search's merged maxima
-    if (a.rorb) {
-        // raw pixels r = a + 128, orbit o as the pairs (r_{o,0} | r_{o,1} << 16), (r_{o,2} | r_{o,3} << 16)
-        uint4* ro = reinterpret_cast<uint4*>(a.rorb + (size_t)gid * 32);
-#pragma unroll
-        for (int v = 0; v < 8; ++v) {
-            uint32_t d[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int o = 2 * v + (e >> 1), k = 2 * (e & 1);
-                d[e] = (uint32_t)(av[kOrb8.p[o][k]] + 128) | ((uint32_t)(av[kOrb8.p[o][k + 1]] + 128) << 16);
-            }
-            ro[v] = make_uint4(d[0], d[1], d[2], d[3]);
-        }
-    }
-    // the block's guard: a 32-lane maximum (whole blocks leave together above), one writer
-    uint32_t g1 = (uint32_t)r1;
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1)
-        g1 = max(g1, (uint32_t)__shfl_xor((int)g1, o, 64));
-    if (col == 0)
-        rguard[b] = g1;
-}
-
-// dft_range_prep_at restated with two lanes per range slot (dft_prep, round 4), as the domain build: lane h
+// The range half: per range block the kDftNBF B fragments (lane l: range slot l&31, orbit 8(l>>5) + j), 16Σa² per
+// slot, the block's guard term max R6 and, for resolve_dft, the slot's pixels in orbit order (rorb).
+// dft_range_prep_pair_at: two lanes per range slot, as the domain build.  Lane h
 // loads rows 4h … 4h + 3 of the range into LDS; each lane then reads the pixels of orbits 8h … 8h + 7 back
 // (T = 8's flipped copies read through the Flip permutation: the same table, another address) and builds that
 // lane half of the fragments and of the orbit-ordered pixel pairs.  Σa² and R6 meet in a lane-pair shuffle;
 // a block's 32 slots are one wave, so its guard stays a wave maximum.
+// T = 8: a block at or past flip_from is the flipped copy of its range, a'(q) = a(Flip q).  Flip_Rotate_k =
+// Flip ∘ Rotate_k (fwd(4 + k, p) = fwd(4, fwd(k, p)), image/transform.h:32-41) and Flip ∘ g^k ∘ Flip = g^−k, so
+// Σ_p a(p)·b(fwd(4 + k, p)) = Σ_q a'(q)·b(g^{−k} q): the copy's rotation t' is transform 4 + (−t' mod 4).
 // RPIX (the SEA tiled form's tp_prep): the range's 64 pixels come from MfmaRangePrepArgs::rpix, the range-order copy
 // the pixel pass stored before the sort (tp_keys): lane h loads its 32-byte half of rpix[ri], no plane row, and the
 // pixel stage is the caller's (lds, 128 slots of kDrRowBytes bytes).
+// ---------------------------------------------------------------------------
 constexpr uint32_t kDrRowBytes = 68; // LDS bytes per slot: 64 + 4 of padding
-template <int FORM, bool RPIX = false>
+template <bool RPIX = false>
 __device__ __forceinline__ void dft_range_prep_pair_at(uint32_t gid2, const MfmaRangePrepArgs& a,
                                                        uint32_t* __restrict__ rguard, uint32_t* lds = nullptr)
 {
-    constexpr int N = 8, NBF = FORM == 6 ? 6 : FORM == 5 ? 5 : kDftRangeFrags;
+    constexpr int N = 8, NBF = kDftNBF;
     constexpr uint32_t kRow = kDrRowBytes;
     uint8_t* px;
     if constexpr (RPIX) {
@@ -732,7 +448,7 @@ __device__ __forceinline__ void dft_range_prep_pair_at(uint32_t gid2, const Mfma
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    // T = 8: the block's flipped copy, a'(q) = a(Flip q) (dft_range_prep_at)
+    // T = 8: the block's flipped copy, a'(q) = a(Flip q)
     const bool flip = ri >= 0 && b >= a.flip_from;
     int av[8][4]; // orbits 8hh … 8hh + 7, their four pixels − 128
 #pragma unroll
@@ -750,29 +466,13 @@ __device__ __forceinline__ void dft_range_prep_pair_at(uint32_t gid2, const Mfma
         const int a0 = av[j][0], a1 = av[j][1], a2 = av[j][2], a3 = av[j][3];
         sa2 += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
         const int sa = a0 + a2, ua = a1 + a3, al = a0 - a2, be = a1 - a3;
-        r1 += FORM == 6 ? abs(sa + ua) + abs(sa - ua) : abs(sa) + abs(ua);
-        if constexpr (FORM == 5) {
-            comp[0][j] = (_Float16)(sa + ua);
-            comp[1][j] = (_Float16)(sa - ua);
-            comp[2][j] = (_Float16)(2 * (al + be));
-            comp[3][j] = (_Float16)(-2 * be);
-            comp[4][j] = (_Float16)(2 * al);
-        } else if constexpr (FORM == 6) {
-            comp[0][j] = (_Float16)(sa + ua);
-            comp[1][j] = (_Float16)(sa - ua);
-            comp[2][j] = (_Float16)(ua - sa);
-            comp[3][j] = (_Float16)(2 * (al + be));
-            comp[4][j] = (_Float16)(-2 * be);
-            comp[5][j] = (_Float16)(2 * al);
-        } else {
-            comp[0][j] = (_Float16)sa;
-            comp[1][j] = (_Float16)ua;
-            comp[2][j] = (_Float16)(4 * sa);
-            comp[3][j] = (_Float16)(4 * ua);
-            comp[4][j] = (_Float16)al;
-            comp[5][j] = (_Float16)be;
-            comp[6][j] = (_Float16)(-al);
-        }
+        r1 += abs(sa + ua) + abs(sa - ua); // guard term R6
+        comp[0][j] = (_Float16)(sa + ua);
+        comp[1][j] = (_Float16)(sa - ua);
+        comp[2][j] = (_Float16)(ua - sa);
+        comp[3][j] = (_Float16)(2 * (al + be));
+        comp[4][j] = (_Float16)(-2 * be);
+        comp[5][j] = (_Float16)(2 * al);
     }
     if (ri < 0) { // an empty slot's fragments are zero (its pixels read as 128 above: already so), no guard
         sa2 = 0;
@@ -807,15 +507,9 @@ __device__ __forceinline__ void dft_range_prep_pair_at(uint32_t gid2, const Mfma
         rguard[b] = g1;
 }
 
-template <int FORM = 4>
-__global__ void __launch_bounds__(256) dft_range_prep(MfmaRangePrepArgs a, uint32_t* __restrict__ rguard)
-{
-    dft_range_prep_at<FORM>(blockIdx.x * blockDim.x + threadIdx.x, a, rguard);
-}
-
 // ---------------------------------------------------------------------------
 // dft_prep: the Fourier path's preparation in one launch.  Blocks [0, dblocks) build the domain
-// tiles (dft_domain_build), the rest prepare the range blocks (dft_range_prep), so the two run
+// tiles (dft_domain_build_pair_at), the rest prepare the range blocks (dft_range_prep_pair_at), so the two run
 // side by side instead of one after the other.  Every thread also takes a grid-stride share of
 // the run's best_key reset, and thread 0 sets the fallback count: the two hipMemsetAsync of
 // launch_all, whose launches cost more than their bytes on small frames.
@@ -830,7 +524,6 @@ struct DftPrepInit {
     uint32_t copies = 1;           // with a plan: range blocks per planned block (T = 8 Fourier: 2)
 };
 
-template <int FORM>
 __global__ void __launch_bounds__(256) dft_prep(MfmaDomainPrepArgs d, DftDomainBuildArgs s, uint2* __restrict__ tguard,
                                                 int32_t* __restrict__ trmax, MfmaRangePrepArgs r,
                                                 uint32_t* __restrict__ rguard, DftPrepInit in)
@@ -846,80 +539,19 @@ __global__ void __launch_bounds__(256) dft_prep(MfmaDomainPrepArgs d, DftDomainB
     if (gt == 0 && in.fb_count)
         *in.fb_count = in.fbc;
     if (blockIdx.x < in.dblocks)
-        dft_domain_build_pair_at<FORM != 4>(gt, d, s, tguard, trmax); // two lanes per tile row
+        dft_domain_build_pair_at(gt, d, s, tguard, trmax); // two lanes per tile row
     else // two lanes per range slot
-        dft_range_prep_pair_at<FORM>((blockIdx.x - in.dblocks) * blockDim.x + threadIdx.x, r, rguard);
+        dft_range_prep_pair_at((blockIdx.x - in.dblocks) * blockDim.x + threadIdx.x, r, rguard);
 }
 
 // ---------------------------------------------------------------------------
-// search_dft<HITS, VAR>: the search_mfma work decomposition (workgroup = 4 waves = 4 range
-// blocks of one bucket, domain tiles staged through LDS, 4 tiles per double-buffered
-// stage); per lane the chunk maximum of y over its 16 rows × the stage's tiles (all four
-// transforms folded in).  Entries: [nwork*4][64] {float bits of max y (+inf = hit), tile}.
-// VAR 1: exact path only (A/B of the guard).
+// search_dft<HITS, VAR>: the search_mfma work decomposition with workgroups of kDftBlocksPerWG waves = range blocks
+// of one bucket, domain tiles staged through LDS, 4 tiles per double-buffered stage; per lane the chunk maximum of
+// h over its 16 rows × the stage's tiles (all four transforms folded in).
 // ---------------------------------------------------------------------------
-__device__ inline floatx16_t mfma2(const half8_t& a0, const half8_t& b0, const half8_t& a1, const half8_t& b1,
-                                   const floatx16_t& c)
-{
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b1, __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0, c, 0, 0, 0),
-                                                  0, 0, 0);
-}
-
-constexpr int kDftChain = 1024;  // VAR bit: v_max3 chain for the row maximum
-
-typedef float float2v_t __attribute__((ext_vector_type(2)));
-
-
-// the five-MFMA form (kDft5): af = [s_b + u_b, s_b − u_b, γ, γ − δ, −δ − γ],
-// bf = [s_a + u_a, s_a − u_a, 2(α + β), −2β, 2α]
-template <bool PK = true>
-__device__ inline float dft_tile_max5(const half8_t (&af)[5], const half8_t (&bf)[5], const floatx16_t& ny, float m)
-{
-    const floatx16_t z = {};
-    const floatx16_t k1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[2], bf[2], z, 0, 0, 0); // 2k1
-    const floatx16_t p = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0], bf[0], z, 0, 0, 0);  // P = U + U'
-    const floatx16_t q = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1], bf[1], z, 0, 0, 0);  // M = U − U'
-    const floatx16_t pr = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[3], bf[3], k1, 0, 0, 0); // 2Pr
-    const floatx16_t pi = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[4], bf[4], k1, 0, 0, 0); // 2Pi
-    float y[16];
-    if constexpr (!PK) {
-        // one row per instruction (A/B of the packed P ± M and fma below)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const float X = p[i] + q[i], Xp = p[i] - q[i];
-            y[i] = __builtin_fmaxf(X + __builtin_fabsf(pr[i]), Xp + __builtin_fabsf(pi[i])) + ny[i]; // h
-        }
-#pragma unroll
-        for (int i = 0; i < 16; i += 2)
-            m = __builtin_fmaxf(__builtin_fmaxf(m, y[i]), y[i + 1]);
-        return m;
-    }
-#pragma unroll
-    for (int i = 0; i < 16; i += 2) {
-        // two rows per packed instruction where no |·| modifier is needed
-        const float2v_t P2 = {p[i], p[i + 1]}, M2 = {q[i], q[i + 1]};
-        const float2v_t X = P2 + M2, Xp = P2 - M2; // 2U, 2U'
-        const float2v_t t = {__builtin_fmaxf(X.x + __builtin_fabsf(pr[i]), Xp.x + __builtin_fabsf(pi[i])),
-                             __builtin_fmaxf(X.y + __builtin_fabsf(pr[i + 1]), Xp.y + __builtin_fabsf(pi[i + 1]))};
-        const float2v_t N2 = {ny[i], ny[i + 1]};
-        const float2v_t yy = t + N2; // h = y/2
-        y[i] = yy.x;
-        y[i + 1] = yy.y;
-    }
-#pragma unroll
-    for (int i = 0; i < 16; i += 2)
-        m = __builtin_fmaxf(__builtin_fmaxf(m, y[i]), y[i + 1]);
-    return m;
-}
-
-// the six-MFMA form (kDft6): af as dft_tile_max5, bf = [s_a + u_a, s_a − u_a, u_a − s_a, 2(α + β), −2β, 2α].
-// The M GEMM accumulates onto P once with +(s_a − u_a) and once with −(s_a − u_a), giving 2U and 2U'
-// in the MFMA (the five-MFMA form's two VALU per candidate for P ± M go away).  Exact in any
-// accumulation order: with A0 = s_a + u_a, A2 = s_a − u_a (B0, B2 on the domain side),
-// |A0| + |A2| = 2·max(|s_a|, |u_a|) ≤ 512 and |B0|, |B2| ≤ 2048, so every partial sum of P ± M is
-// bounded by Σ_o (|A0·B0| + |A2·B2|) ≤ 16·2048·512 = 2^24.  Then the exact form's epilogue:
-//   h = max(2U + |2Pr|, 2U' + |2Pi|) − Σb²/2   (ny = −Σb²/2; y = 2h).
-__device__ inline float dft_tile_max6(const half8_t (&af)[5], const half8_t (&bf)[6], const floatx16_t& ny, float m)
+// The exact epilogue, row constants in registers (kDftExactVar).  af: the tile's fragments, bf: the block's (the head
+// comment); ny = −Σb²/2:  h = max(2U + |2Pr|, 2U' + |2Pi|) − Σb²/2.
+__device__ inline float dft_tile_max6(const half8_t (&af)[kDftKS], const half8_t (&bf)[kDftNBF], const floatx16_t& ny, float m)
 {
     const floatx16_t z = {};
     const floatx16_t p = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0], bf[0], z, 0, 0, 0);  // P
@@ -938,162 +570,6 @@ __device__ inline float dft_tile_max6(const half8_t (&af)[5], const half8_t (&bf
     return m;
 }
 
-// The guarded fast path (kDftFast6, exactness above kFast6Limit): P starts from C = −Σb²/2, so u' and
-// v' carry the row constant and a candidate costs u' + |2Pr|, v' + |2Pi| and one step of a v_max3
-// chain.  Only for tile pairs whose guard holds.
-__device__ inline float dft_tile_max6_fast(const half8_t (&af)[5], const half8_t (&bf)[6], const floatx16_t& ny,
-                                           float m)
-{
-    const floatx16_t z = {};
-    const floatx16_t k1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[2], bf[3], z, 0, 0, 0); // 2k1
-    const floatx16_t p = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0], bf[0], ny, 0, 0, 0); // P − Σb²/2
-    const floatx16_t pr = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[3], bf[4], k1, 0, 0, 0); // 2Pr
-    const floatx16_t u = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1], bf[1], p, 0, 0, 0);  // 2U − Σb²/2
-    const floatx16_t pi = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[4], bf[5], k1, 0, 0, 0); // 2Pi
-    const floatx16_t v = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1], bf[2], p, 0, 0, 0);  // 2U' − Σb²/2
-#pragma unroll
-    for (int i = 0; i < 16; ++i)
-        m = __builtin_fmaxf(__builtin_fmaxf(m, u[i] + __builtin_fabsf(pr[i])), v[i] + __builtin_fabsf(pi[i]));
-    return m;
-}
-
-// The six-MFMA form for two range blocks sharing one domain tile (search_dft2<…, true>): the tile's
-// A fragments and row constants are read once for both blocks.
-__device__ inline void dft_tile_max6x2(const half8_t (&af)[5], const half8_t (&ba)[6], const half8_t (&bb)[6],
-                                       const floatx16_t& ny, float& ma, float& mb)
-{
-    const floatx16_t z = {};
-    const floatx16_t pa = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0], ba[0], z, 0, 0, 0);
-    const floatx16_t pb = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0], bb[0], z, 0, 0, 0);
-    const floatx16_t ka = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[2], ba[3], z, 0, 0, 0);
-    const floatx16_t kb = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[2], bb[3], z, 0, 0, 0);
-    const floatx16_t ua = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1], ba[1], pa, 0, 0, 0);
-    const floatx16_t ub = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1], bb[1], pb, 0, 0, 0);
-    const floatx16_t ra = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[3], ba[4], ka, 0, 0, 0);
-    const floatx16_t rb = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[3], bb[4], kb, 0, 0, 0);
-    const floatx16_t va = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1], ba[2], pa, 0, 0, 0);
-    const floatx16_t vb = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1], bb[2], pb, 0, 0, 0);
-    const floatx16_t ia = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[4], ba[5], ka, 0, 0, 0);
-    const floatx16_t ib = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[4], bb[5], kb, 0, 0, 0);
-    float ya[16], yb[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { // h = y/2 (ny = −Σb²/2)
-        ya[i] = __builtin_fmaxf(ua[i] + __builtin_fabsf(ra[i]), va[i] + __builtin_fabsf(ia[i])) + ny[i];
-        yb[i] = __builtin_fmaxf(ub[i] + __builtin_fabsf(rb[i]), vb[i] + __builtin_fabsf(ib[i])) + ny[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 16; i += 2) {
-        ma = __builtin_fmaxf(__builtin_fmaxf(ma, ya[i]), ya[i + 1]);
-        mb = __builtin_fmaxf(__builtin_fmaxf(mb, yb[i]), yb[i + 1]);
-    }
-}
-
-template <int VAR>
-__device__ inline float dft_tile_max4(const half8_t (&af)[4], const half8_t (&bf)[kDftRangeFrags],
-                                      const floatx16_t& ny, bool fast, float m)
-{
-    const floatx16_t z = {};
-    // af: [s_b, u_b, γ, δ];  bf: [s_a, u_a, 4s_a, 4u_a, α, β, −α]
-    if constexpr ((VAR & 16) != 0) {
-        // ABLATION (tuning only, wrong results): the exact epilogue on fake accumulators
-        floatx16_t u, v, pr, pi;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const float b = __builtin_bit_cast(float, __builtin_bit_cast(uint4, af[i & 3]).x);
-            u[i] = b + (float)i;
-            v[i] = b - (float)i;
-            pr[i] = b * 0.5f;
-            pi[i] = ny[i];
-        }
-        float m2 = m;
-#pragma unroll
-        for (int i = 0; i < 16; i += 2) {
-            const float y0 = __builtin_fmaf(
-                __builtin_fmaxf(u[i] + __builtin_fabsf(pr[i]), v[i] + __builtin_fabsf(pi[i])), 4.0f, ny[i]);
-            const float y1 = __builtin_fmaf(__builtin_fmaxf(u[i + 1] + __builtin_fabsf(pr[i + 1]),
-                                                            v[i + 1] + __builtin_fabsf(pi[i + 1])),
-                                            4.0f, ny[i + 1]);
-            m2 = __builtin_fmaxf(m2, __builtin_fmaxf(y0, y1));
-        }
-        (void)bf;
-        (void)fast;
-        return m2;
-    }
-    const floatx16_t pr = mfma2(af[2], bf[4], af[3], bf[5], z);
-    float m0 = m, m1 = -__builtin_inff();
-    if ((VAR & 1) == 0 && fast) {
-        const floatx16_t pi = mfma2(af[2], bf[5], af[3], bf[6], z);
-        const floatx16_t u = mfma2(af[0], bf[2], af[1], bf[3], ny);  // 4U − Σb²
-        const floatx16_t v = mfma2(af[0], bf[3], af[1], bf[2], ny);  // 4U' − Σb²
-#pragma unroll
-        for (int i = 0; i < 16; i += 2) {
-            m0 = __builtin_fmaxf(m0, __builtin_fmaxf(__builtin_fmaf(__builtin_fabsf(pr[i]), 4.0f, u[i]),
-                                                     __builtin_fmaf(__builtin_fabsf(pi[i]), 4.0f, v[i])));
-            m1 = __builtin_fmaxf(m1, __builtin_fmaxf(__builtin_fmaf(__builtin_fabsf(pr[i + 1]), 4.0f, u[i + 1]),
-                                                     __builtin_fmaf(__builtin_fabsf(pi[i + 1]), 4.0f, v[i + 1])));
-        }
-    } else if constexpr ((VAR & 8) != 0) {
-        // ABLATION (tuning only, wrong results): MFMAs with a one-value epilogue
-        const floatx16_t pi = mfma2(af[2], bf[5], af[3], bf[6], z);
-        const floatx16_t u = mfma2(af[0], bf[0], af[1], bf[1], z);
-        const floatx16_t v = mfma2(af[0], bf[1], af[1], bf[0], z);
-        m0 = __builtin_fmaxf(m0, u[0] + v[0] + pr[0] + pi[0] + ny[0]);
-    } else if constexpr ((VAR & kDftChain) != 0) {
-        // the row maximum as one v_max3 chain over the 16 candidates (8 instead of the 12 the
-        // pairwise tree below compiles to): 76 instead of 80 VALU per tile pair in the loop,
-        // −1.3 % search time in a 20-round interleaved A/B (tools/ab_mfma.py d,dc)
-        const floatx16_t u = mfma2(af[0], bf[0], af[1], bf[1], z);   // U
-        const floatx16_t v = mfma2(af[0], bf[1], af[1], bf[0], z);   // U'
-        const floatx16_t pi = mfma2(af[2], bf[5], af[3], bf[6], z);  // Pi
-        float y[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-            y[i] = __builtin_fmaf(__builtin_fmaxf(u[i] + __builtin_fabsf(pr[i]), v[i] + __builtin_fabsf(pi[i])), 4.0f,
-                                  ny[i]);
-#pragma unroll
-        for (int i = 0; i < 16; i += 2)
-            m0 = __builtin_fmaxf(__builtin_fmaxf(m0, y[i]), y[i + 1]);
-        return m0;
-    } else {
-        const floatx16_t u = mfma2(af[0], bf[0], af[1], bf[1], z);   // U
-        const floatx16_t v = mfma2(af[0], bf[1], af[1], bf[0], z);   // U'
-        const floatx16_t pi = mfma2(af[2], bf[5], af[3], bf[6], z);  // Pi
-#pragma unroll
-        for (int i = 0; i < 16; i += 2) {
-            const float y0 = __builtin_fmaf(
-                __builtin_fmaxf(u[i] + __builtin_fabsf(pr[i]), v[i] + __builtin_fabsf(pi[i])), 4.0f, ny[i]);
-            const float y1 = __builtin_fmaf(
-                __builtin_fmaxf(u[i + 1] + __builtin_fabsf(pr[i + 1]), v[i + 1] + __builtin_fabsf(pi[i + 1])), 4.0f,
-                ny[i + 1]);
-            m0 = __builtin_fmaxf(m0, __builtin_fmaxf(y0, y1));
-        }
-    }
-    return __builtin_fmaxf(m0, m1);
-}
-
-template <int VAR>
-__device__ inline float dft_tile_max(const half8_t (&af)[DftForm<VAR>::KS], const half8_t (&bf)[DftForm<VAR>::NBF],
-                                     const floatx16_t& ny, bool fast, float m)
-{
-    if constexpr (DftForm<VAR>::F5) {
-        static_assert((VAR & 1) != 0, "the five-MFMA form has no guarded fast path");
-        (void)fast;
-        return dft_tile_max5<(VAR & kDftScalar) == 0>(af, bf, ny, m);
-    } else if constexpr (DftForm<VAR>::F6) {
-        static_assert((VAR & 1) != 0, "the six-MFMA form's guarded path is kDftFast6");
-        if constexpr (DftForm<VAR>::FAST6) {
-            if (fast)
-                return dft_tile_max6_fast(af, bf, ny, m);
-        }
-        (void)fast;
-        return dft_tile_max6(af, bf, ny, m);
-    } else {
-        return dft_tile_max4<VAR>(af, bf, ny, fast, m);
-    }
-}
-
-// MASK (CHUNKED search): masks[0] gets the chunk tiles attaining the lane's maximum, masks[1]
-// (HITS) the tiles holding a hit (y ≥ hl), bit k for tile q0 + k
 __device__ inline floatx16_t lds_row_consts(const uint4* p)
 {
     floatx16_t r;
@@ -1108,14 +584,14 @@ __device__ inline floatx16_t lds_row_consts(const uint4* p)
     return r;
 }
 
-// One tile pair of the six-MFMA form with the guarded fast path (kDftFast6).  Both paths issue
+// One tile pair with the guarded fast path (kDftFast6, kDftFastVar).  Both paths issue
 // the same six MFMAs; only P's C operand differs — the tile's −Σb²/2 row constants when the guard
 // holds, the stage's zero block when it does not (a wave-uniform choice of address, so one MFMA
 // sequence and one register allocation serve both) — and the epilogue: the folded form
 // (2 VALU + one v_max3 step per candidate), or the exact one with the constants read after the
 // MFMAs.  lc: the tile's row constants ([2][16] lane-half layout), h: the lane half.
 template <int ABL = 0>
-__device__ inline float dft_tile_max6g(const half8_t (&af)[5], const half8_t (&bf)[6], const uint4* la, uint32_t ic,
+__device__ inline float dft_tile_max6g(const half8_t (&af)[kDftKS], const half8_t (&bf)[kDftNBF], const uint4* la, uint32_t ic,
                                        uint32_t iz, uint32_t h, bool fast, float m)
 {
     if constexpr (ABL == 16) {
@@ -1172,14 +648,17 @@ __device__ inline uint32_t dft_guard_bits(const int32_t* __restrict__ trmax, uin
     return g & ((1u << ne) - 1u);
 }
 
+// One 4-tile chunk [q0, q1) of the stage at la (nt tiles): the lane's maximum of h over it.
+// MASK (CHUNKED or TMASK search): masks[0] gets the chunk tiles attaining the lane's maximum, masks[1]
+// (HITS) the tiles holding a hit (h ≥ hl), bit k for tile q0 + k.  iz: the stage's zero block (kDftFast6).
 template <int VAR, bool MASK = false, bool HITS = false>
 __device__ inline float dft_compute_stage(const uint4* __restrict__ la, uint32_t nt, uint32_t lane,
-                                          const half8_t (&bf)[DftForm<VAR>::NBF], uint32_t tb,
-                                          const uint2* __restrict__ tguard, uint32_t r1, uint32_t q0 = 0,
-                                          uint32_t q1 = ~0u, uint32_t* masks = nullptr, float hl = 0.0f,
-                                          uint32_t iz = 0, const int32_t* __restrict__ trmax = nullptr)
+                                          const half8_t (&bf)[kDftNBF], uint32_t tb, uint32_t r1, uint32_t q0,
+                                          uint32_t q1, uint32_t* masks, float hl, uint32_t iz,
+                                          const int32_t* __restrict__ trmax)
 {
-    constexpr int KS = DftForm<VAR>::KS;
+    constexpr int KS = kDftKS;
+    constexpr bool FAST6 = DftForm<VAR>::FAST6;
     const uint4* lc = la + nt * (uint32_t)KS * 64u;
     const uint32_t h = lane >> 5;
     float cm = -__builtin_inff();
@@ -1188,17 +667,8 @@ __device__ inline float dft_compute_stage(const uint4* __restrict__ la, uint32_t
     // the tile index is wave-uniform: readfirstlane + the constant address space make the guard
     // loads scalar, which the vmcnt waits of the stage's LDS-DMA do not serialise with
     const uint32_t t0 = __builtin_amdgcn_readfirstlane(tb + q0), ne = __builtin_amdgcn_readfirstlane(min(q1, nt) - q0);
-    if constexpr (DftForm<VAR>::FAST6) {
+    if constexpr (FAST6)
         gfast = dft_guard_bits(trmax, t0, ne, r1);
-    } else if constexpr ((VAR & 1) == 0) {
-#pragma unroll
-        for (uint32_t k = 0; k < 4; ++k)
-            if (k < ne) {
-                const __attribute__((address_space(4))) uint32_t* gp =
-                    (const __attribute__((address_space(4))) uint32_t*)(uintptr_t)(tguard + t0 + k);
-                gfast |= ((uint64_t)r1 * gp[0] + gp[1] <= (uint64_t)kExactLimit) ? (1u << k) : 0u;
-            }
-    }
     auto tile = [&](uint32_t q) {
         // ABLATION bit 32 (tuning only, wrong results): every tile reuses tile 0's operands
         const uint32_t qq = (VAR & 32) ? 0u : q;
@@ -1206,45 +676,29 @@ __device__ inline float dft_compute_stage(const uint4* __restrict__ la, uint32_t
 #pragma unroll
         for (int s = 0; s < KS; ++s)
             af[s] = __builtin_bit_cast(half8_t, la[(qq * KS + s) * 64 + lane]);
-        if constexpr (DftForm<VAR>::FAST6) {
-            const bool fast = (gfast >> (q - q0)) & 1u;
-            const uint32_t ic = nt * (uint32_t)KS * 64u + qq * kDftCS;
-            if constexpr (MASK) { // TMASK: the tile's own maximum first, then the chunk's tiles attaining it
-                const float tm = dft_tile_max6g<VAR & (8 | 16)>(af, bf, la, ic, iz, h, fast, -__builtin_inff());
-                const uint32_t bit = 1u << (q - q0);
-                masks[0] = tm > cm ? bit : (tm == cm ? masks[0] | bit : masks[0]);
-                if constexpr (HITS)
-                    masks[1] |= tm >= hl ? bit : 0u;
-                cm = __builtin_fmaxf(cm, tm);
+        // the tile's maximum folded onto m
+        auto tile_max = [&](float m) {
+            if constexpr (FAST6) {
+                const bool fast = (gfast >> (q - q0)) & 1u; // wave-uniform
+                const uint32_t ic = nt * (uint32_t)KS * 64u + qq * kDftCS;
+                return dft_tile_max6g<VAR & (8 | 16)>(af, bf, la, ic, iz, h, fast, m);
             } else {
-                cm = dft_tile_max6g<VAR & (8 | 16)>(af, bf, la, ic, iz, h, fast, cm);
+                return dft_tile_max6(af, bf, lds_row_consts(lc + qq * kDftCS + h * 4), m);
             }
-            return;
-        }
-        floatx16_t ny;
-#pragma unroll
-        for (int c4 = 0; c4 < 4; ++c4) {
-            const uint4 v = lc[qq * kDftCS + h * 4 + c4];
-            ny[4 * c4 + 0] = __uint_as_float(v.x);
-            ny[4 * c4 + 1] = __uint_as_float(v.y);
-            ny[4 * c4 + 2] = __uint_as_float(v.z);
-            ny[4 * c4 + 3] = __uint_as_float(v.w);
-        }
-        // wave-uniform guard: every partial sum of 4U − Σb² stays within 2^24
-        const bool fast = (gfast >> (q - q0)) & 1u;
-        if constexpr (MASK) {
-            const float tm = dft_tile_max<VAR>(af, bf, ny, fast, -__builtin_inff());
+        };
+        if constexpr (MASK) { // the tile's own maximum first, then the chunk's tiles attaining it
+            const float tm = tile_max(-__builtin_inff());
             const uint32_t bit = 1u << (q - q0);
             masks[0] = tm > cm ? bit : (tm == cm ? masks[0] | bit : masks[0]);
             if constexpr (HITS)
                 masks[1] |= tm >= hl ? bit : 0u;
             cm = __builtin_fmaxf(cm, tm);
         } else {
-            cm = dft_tile_max<VAR>(af, bf, ny, fast, cm);
+            cm = tile_max(cm);
         }
     };
     const uint32_t qe = min(q1, nt);
-    if constexpr ((VAR & kDftUnroll) != 0) {
+    if constexpr (FAST6) { // the chunk unrolled
 #pragma unroll
         for (uint32_t k = 0; k < 4; ++k)
             if (q0 + k < qe)
@@ -1256,53 +710,54 @@ __device__ inline float dft_compute_stage(const uint4* __restrict__ la, uint32_t
     return cm;
 }
 
-// stage_tiles by buffer_load … lds in whole-wave pieces (1 KiB each): the stage's nt·KS A-fragment
-// pieces and its one constants piece (kDftCS = 16 uint4 per tile: 4 tiles are one piece; a shorter
-// last stage reads the next tiles' constants or the allocation's 1 KiB of slack, never used).  The
-// loop, the LDS destination (M0) and the source offset (soffset) are wave-uniform: every piece costs
-// scalar instructions only, the lane's voffset (lane·16) is fixed.
-template <int KS, uint32_t WAVES>
-__device__ inline void stage_tiles_buf(uint4* dst, __amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rc, uint32_t tb,
-                                       uint32_t nt)
-{
-    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t voff = (threadIdx.x & 63u) * 16u;
-    const uint32_t tbu = __builtin_amdgcn_readfirstlane(tb), npa = __builtin_amdgcn_readfirstlane(nt * (uint32_t)KS);
-    for (uint32_t p = wv; p <= npa; p += WAVES) {
-        auto* l = (__attribute__((address_space(3))) void*)(dst + p * 64u);
-        if (p < npa)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, l, 16, voff, (tbu * (uint32_t)KS + p) * 1024u, 0, 0);
-        else
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rc, l, 16, voff, tbu * kDftCS * 16u, 0, 0);
-    }
-}
-
 constexpr uint32_t kDftBlocksPerWG = 8; // waves (range blocks) sharing one LDS domain stage
 // chunks a CHUNKED record lists by word (K of DESIGN §7.7); its count of attaining chunks is exact, so
 // the resolve tells "all listed" from "more than listed"
 constexpr uint32_t kTpRecList = 2;
 
+// stage_tiles by buffer_load … lds in whole-wave pieces (1 KiB each): the stage's nt·kDftKS A-fragment
+// pieces and its one constants piece (kDftCS = 16 uint4 per tile: 4 tiles are one piece; a shorter
+// last stage reads the next tiles' constants or the allocation's 1 KiB of slack, never used).  The
+// loop, the LDS destination (M0) and the source offset (soffset) are wave-uniform: every piece costs
+// scalar instructions only, the lane's voffset (lane·16) is fixed.
+__device__ inline void stage_tiles_buf(uint4* dst, __amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rc, uint32_t tb,
+                                       uint32_t nt)
+{
+    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    constexpr uint32_t KS = kDftKS, WAVES = kDftBlocksPerWG;
+    const uint32_t voff = (threadIdx.x & 63u) * 16u;
+    const uint32_t tbu = __builtin_amdgcn_readfirstlane(tb), npa = __builtin_amdgcn_readfirstlane(nt * KS);
+    for (uint32_t p = wv; p <= npa; p += WAVES) {
+        auto* l = (__attribute__((address_space(3))) void*)(dst + p * 64u);
+        if (p < npa)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, l, 16, voff, (tbu * KS + p) * 1024u, 0, 0);
+        else
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rc, l, 16, voff, tbu * kDftCS * 16u, 0, 0);
+    }
+}
+
 // CHUNKED (the SEA engine's tiled form, fracenc_tp.hip): tiles are in ΣD4 order, not domain
 // order, so every chunk attaining a lane's maximum matters, not only the first.  One workgroup holds a
 // group's whole window and wave w its block wk.x + w throughout, so the lane keeps the running maximum,
 // the number of chunks attaining it and the words of the first kTpRecList of them in registers, and
-// writes one record per lane when the window is done (DftArgs::rec): no per-chunk entries.  resolve_dft
+// writes one record per lane when the window is done (DftArgs::rec).  resolve_dft
 // re-evaluates the listed chunks, or the whole window when more than the list holds attain the maximum.
 // TMASK (not CHUNKED, slotbest): each lane also tracks which tiles of its best chunk attain its maximum (or
 // hold a hit), and the slot word carries them, so resolve_dft re-evaluates those tiles instead of the whole
 // chunk.  Costs the tile-pair epilogue a compare per tile: chosen where the resolve, not the search, dominates.
-template <bool HITS, int VAR, uint32_t WAVES = 4, uint32_t TPS = kTilesPerStage, bool CHUNKED = false,
-          bool TMASK = false>
-__global__ void __launch_bounds__(64 * WAVES) search_dft(DftArgs d)
+template <bool HITS, int VAR, bool CHUNKED = false, bool TMASK = false>
+__global__ void __launch_bounds__(64 * kDftBlocksPerWG) search_dft(DftArgs d)
 {
+    constexpr uint32_t WAVES = kDftBlocksPerWG;
+    constexpr uint32_t kTilesPerStage = fracenc::kTilesPerStage; // LDS stage = chunk (resolve_dft): unsigned here
+    static_assert(kTilesPerStage == 4, "chunk words, tile masks and the guard load assume 4-tile stages");
     static_assert(kTuningBuild || (VAR & (8 | 16 | 32 | 64 | 256 | 512)) == 0,
                   "search_dft ablations exist only in FRAC_TUNING builds");
-    static_assert(!(TMASK && CHUNKED), "CHUNKED entries carry their own tile masks");
+    static_assert(!(TMASK && CHUNKED), "CHUNKED records carry their own tile masks");
     if (past_plan(d.m))
         return;
     const MfmaSearchArgs& a = d.m;
-    constexpr int KS = DftForm<VAR>::KS, NBF = DftForm<VAR>::NBF;
-    constexpr uint32_t kTilesPerStage = TPS; // LDS stage; chunks stay 4 tiles (resolve_dft)
+    constexpr int KS = kDftKS, NBF = kDftNBF;
     constexpr int STAGE = kTilesPerStage * KS * 64 + kTilesPerStage * kDftCS;
     // kDftFast6: each stage buffer ends in 8 zero uint4, the row constants of a tile pair that runs
     // the exact epilogue (written here, published by the first stage barrier, never a DMA target).
@@ -1314,8 +769,7 @@ __global__ void __launch_bounds__(64 * WAVES) search_dft(DftArgs d)
     if constexpr (DftForm<VAR>::FAST6)
         if (threadIdx.x < 2 * ZTAIL)
             (threadIdx.x < ZTAIL ? lds0 : lds1)[STAGE + (threadIdx.x % ZTAIL)] = make_uint4(0u, 0u, 0u, 0u);
-    // (everything below is indexed by the work item's blocks and tiles; blockIdx.x itself only by the
-    // not-CHUNKED entries)
+    // (everything below is indexed by the work item's blocks and tiles, not by blockIdx.x)
     const uint4 wk = a.work[(CHUNKED && d.order) ? d.order[blockIdx.x] : blockIdx.x];
     const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const bool active = wv < wk.y;
@@ -1329,11 +783,10 @@ __global__ void __launch_bounds__(64 * WAVES) search_dft(DftArgs d)
     float hl = 0.0f;
     if constexpr (HITS) { // S16 ≤ H  ⇔  y ≥ 16Σa² − H  (exact integers below 2^24; halved exactly for h)
         hl = (float)((int32_t)a.rconst[blk * 32 + (lane & 31u)] - (int32_t)a.hitH);
-        if constexpr (DftForm<VAR>::HALF)
-            hl *= 0.5f;
+        hl *= 0.5f;
     }
-    // the forms that track h = y/2 store y = 2h (exact) in the entries
-    constexpr float kOut = DftForm<VAR>::HALF ? 2.0f : 1.0f;
+    // the search tracks h = y/2; the records and slot words carry y = 2h (exact)
+    constexpr float kOut = 2.0f;
 
     float best = -__builtin_inff();
     uint32_t btile = 0, bmask = 0xfu;
@@ -1341,7 +794,6 @@ __global__ void __launch_bounds__(64 * WAVES) search_dft(DftArgs d)
     uint32_t nbest = 0, word1 = 0, word2 = 0; // CHUNKED: chunks attaining `best`, the first two's words
     auto finish_stage = [&](float cm, uint32_t tb) {
         if constexpr (CHUNKED) {
-            static_assert(TPS == 4, "chunk words assume 4-tile stages");
             static_assert(kTpRecList == 2, "the record lists two chunks");
             // the chunk's word carries its tile mask in bits 28..31 of its tile (resolve_dft<true>
             // evaluates only those tiles): the hit tiles when the chunk holds a hit, else the
@@ -1363,7 +815,7 @@ __global__ void __launch_bounds__(64 * WAVES) search_dft(DftArgs d)
             return;
         }
         // any hit in the chunk: the first-hit chunk wins. (A per-tile mask here, as the CHUNKED
-        // entries carry, cost 4% of this kernel in a 30-sample A/B for 0.1 ms less resolve: only TMASK.)
+        // records carry, cost 4% of this kernel in a 30-sample A/B for 0.1 ms less resolve: only TMASK.)
         uint32_t msk = 0xfu;
         if constexpr (TMASK) {
             msk = masks[0];
@@ -1386,16 +838,12 @@ __global__ void __launch_bounds__(64 * WAVES) search_dft(DftArgs d)
     constexpr bool NODMA = (VAR & 64) != 0;
     constexpr bool SKIPDMA = NODMA || (VAR & 256) != 0, SKIPBAR = NODMA || (VAR & 512) != 0;
     auto stage = [&](uint4* dst, uint32_t tb, uint32_t nt) {
-        if constexpr ((VAR & kDftBufDma) != 0) // raw buffers (no range check: the pieces are in bounds)
-            stage_tiles_buf<KS, WAVES>(
-                dst, __builtin_amdgcn_make_buffer_rsrc((void*)a.dtiles, 0, 0xffffffffu, 0x00020000),
-                __builtin_amdgcn_make_buffer_rsrc((void*)a.dconst, 0, 0xffffffffu, 0x00020000), tb, nt);
+        if constexpr (DftForm<VAR>::FAST6) // raw buffers (no range check: the pieces are in bounds)
+            stage_tiles_buf(dst, __builtin_amdgcn_make_buffer_rsrc((void*)a.dtiles, 0, 0xffffffffu, 0x00020000),
+                            __builtin_amdgcn_make_buffer_rsrc((void*)a.dconst, 0, 0xffffffffu, 0x00020000), tb, nt);
         else
             stage_tiles<KS, 64 * WAVES, kDftCS>(dst, a.dtiles, a.dconst, tb, nt);
     };
-    if constexpr ((VAR & kDftPrio) != 0)
-        if (wv >= WAVES / 2)
-            __builtin_amdgcn_s_setprio(1);
 #ifdef FRAC_CLOCK_STAMP
     // diagnostic build only (tools/clock_stamp.py, MI355X_MICROARCH.md "DVFS give-back"): the shader
     // clock over this workgroup's loop is Δs_memtime ÷ Δs_memrealtime × 100 MHz
@@ -1411,8 +859,8 @@ __global__ void __launch_bounds__(64 * WAVES) search_dft(DftArgs d)
             if (st + 1 < nstage && (!SKIPDMA || st == 0))
                 stage(lds1, tb + kTilesPerStage, stage_nt(st + 1));
             for (uint32_t c0 = 0; c0 < stage_nt(st); c0 += 4)
-                finish_stage(dft_compute_stage<VAR, CHUNKED || TMASK, HITS>(lds0, stage_nt(st), lane, bf, tb, d.tguard, r1, c0,
-                                                                   c0 + 4, masks, hl, STAGE, d.trmax),
+                finish_stage(dft_compute_stage<VAR, CHUNKED || TMASK, HITS>(lds0, stage_nt(st), lane, bf, tb, r1, c0, c0 + 4,
+                                                                            masks, hl, STAGE, d.trmax),
                              tb + c0);
         }
         if (st + 1 < nstage) {
@@ -1422,8 +870,8 @@ __global__ void __launch_bounds__(64 * WAVES) search_dft(DftArgs d)
             if (st + 2 < nstage && !SKIPDMA)
                 stage(lds0, tb + kTilesPerStage, stage_nt(st + 2));
             for (uint32_t c0 = 0; c0 < stage_nt(st + 1); c0 += 4)
-                finish_stage(dft_compute_stage<VAR, CHUNKED || TMASK, HITS>(lds1, stage_nt(st + 1), lane, bf, tb, d.tguard, r1,
-                                                                   c0, c0 + 4, masks, hl, STAGE, d.trmax),
+                finish_stage(dft_compute_stage<VAR, CHUNKED || TMASK, HITS>(lds1, stage_nt(st + 1), lane, bf, tb, r1, c0,
+                                                                            c0 + 4, masks, hl, STAGE, d.trmax),
                              tb + c0);
         }
     }
@@ -1447,131 +895,29 @@ __global__ void __launch_bounds__(64 * WAVES) search_dft(DftArgs d)
             d.rec[(size_t)blk * 64 + lane] = make_uint4(__float_as_uint(best * kOut), nbest, word1, word2);
     }
     if (active && !CHUNKED) {
-        if (d.slotbest) {
-            // lanes l and l + 32 hold one range slot's two row halves: the greater y, among equal y the earlier
-            // chunk, and which halves attain it there (both: resolve_dft evaluates both halves' rows)
-            const uint32_t y0 = fmap(best * kOut), t0 = btile;
-            const uint32_t y1 = (uint32_t)__shfl_xor((int)y0, 32, 64), t1 = (uint32_t)__shfl_xor((int)t0, 32, 64);
-            const uint32_t m1 = TMASK ? (uint32_t)__shfl_xor((int)bmask, 32, 64) : 0xfu;
-            const bool first = lane < 32u;
-            const uint32_t ym = first ? y0 : y1, tm = first ? t0 : t1; // this half (lane < 32: half 0)
-            const uint32_t yo = first ? y1 : y0, to = first ? t1 : t0; // the other half
-            if (first) {
-                uint32_t tile = tm, hm = 1u, mk = bmask;
-                if (yo > ym || (yo == ym && to < tm)) {
-                    tile = to;
-                    hm = 2u;
-                    mk = m1;
-                } else if (yo == ym && to == tm) {
-                    hm = 3u;
-                    mk |= m1; // both halves' rows are evaluated on every tile of the union
-                }
-                const unsigned long long w = ((unsigned long long)max(ym, yo) << 32) |
-                                             ((kSlotBestTileMax - tile) << 6) | (mk << 2) | hm;
-                atomicMax(d.slotbest + (size_t)blk * 32 + lane, w);
+        // lanes l and l + 32 hold one range slot's two row halves: the greater y, among equal y the earlier
+        // chunk, and which halves attain it there (both: resolve_dft evaluates both halves' rows)
+        const uint32_t y0 = fmap(best * kOut), t0 = btile;
+        const uint32_t y1 = (uint32_t)__shfl_xor((int)y0, 32, 64), t1 = (uint32_t)__shfl_xor((int)t0, 32, 64);
+        const uint32_t m1 = TMASK ? (uint32_t)__shfl_xor((int)bmask, 32, 64) : 0xfu;
+        const bool first = lane < 32u;
+        const uint32_t ym = first ? y0 : y1, tm = first ? t0 : t1; // this half (lane < 32: half 0)
+        const uint32_t yo = first ? y1 : y0, to = first ? t1 : t0; // the other half
+        if (first) {
+            uint32_t tile = tm, hm = 1u, mk = bmask;
+            if (yo > ym || (yo == ym && to < tm)) {
+                tile = to;
+                hm = 2u;
+                mk = m1;
+            } else if (yo == ym && to == tm) {
+                hm = 3u;
+                mk |= m1; // both halves' rows are evaluated on every tile of the union
             }
-        } else {
-            a.entries[(size_t)(blockIdx.x * WAVES + wv) * 64 + lane] = make_uint2(__float_as_uint(best * kOut), btile);
+            const unsigned long long w = ((unsigned long long)max(ym, yo) << 32) |
+                                         ((kSlotBestTileMax - tile) << 6) | (mk << 2) | hm;
+            atomicMax(d.slotbest + (size_t)blk * 32 + lane, w);
         }
     }
-}
-
-// ---------------------------------------------------------------------------
-// search_dft2<HITS>: the exact form with two range blocks per wave (4-wave workgroups, 8 blocks
-// per workgroup, the entry layout of search_dft<…, 8>): a tile's A fragments and −Σb² row
-// constants are read from LDS once for both blocks, half the LDS bytes per (block, tile) pair.
-// 3 waves per SIMD (3 workgroups per CU) instead of 4.
-// ---------------------------------------------------------------------------
-// F6: the six-MFMA form (dft_tile_max6x2), 2 waves per SIMD
-template <bool HITS, bool F6 = false>
-__global__ void __launch_bounds__(256, F6 ? 2 : 3) search_dft2(DftArgs d)
-{
-    const MfmaSearchArgs& a = d.m;
-    constexpr int VAR = 1 | kDftChain | (F6 ? kDft6 : 0);
-    constexpr int KS = DftForm<VAR>::KS, NBF = DftForm<VAR>::NBF;
-    constexpr int STAGE = kTilesPerStage * KS * 64 + kTilesPerStage * kDftCS;
-    __shared__ uint4 lds0[STAGE];
-    __shared__ uint4 lds1[STAGE];
-    const uint4 wk = a.work[blockIdx.x];
-    const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    bool act[2];
-    half8_t bf[2][NBF];
-    float hl[2] = {0.0f, 0.0f}, best[2];
-    uint32_t btile[2] = {0u, 0u};
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const uint32_t b = 2 * wv + k;
-        act[k] = b < wk.y;
-        const uint32_t blk = wk.x + (act[k] ? b : 0u);
-#pragma unroll
-        for (int f = 0; f < NBF; ++f)
-            bf[k][f] = __builtin_bit_cast(half8_t, a.rfrags[((size_t)blk * NBF + f) * 64 + lane]);
-        if constexpr (HITS)
-            hl[k] = (float)((int32_t)a.rconst[blk * 32 + (lane & 31u)] - (int32_t)a.hitH) * (F6 ? 0.5f : 1.0f);
-        best[k] = -__builtin_inff();
-    }
-    const uint32_t h = lane >> 5;
-    auto compute = [&](const uint4* la, uint32_t nt, uint32_t tb) {
-        const uint4* lc = la + nt * (uint32_t)KS * 64u;
-        float cm[2] = {-__builtin_inff(), -__builtin_inff()};
-        for (uint32_t q = 0; q < nt; ++q) {
-            half8_t af[KS];
-#pragma unroll
-            for (int s = 0; s < KS; ++s)
-                af[s] = __builtin_bit_cast(half8_t, la[(q * KS + s) * 64 + lane]);
-            floatx16_t ny;
-#pragma unroll
-            for (int c4 = 0; c4 < 4; ++c4) {
-                const uint4 v = lc[q * kDftCS + h * 4 + c4];
-                ny[4 * c4 + 0] = __uint_as_float(v.x);
-                ny[4 * c4 + 1] = __uint_as_float(v.y);
-                ny[4 * c4 + 2] = __uint_as_float(v.z);
-                ny[4 * c4 + 3] = __uint_as_float(v.w);
-            }
-            if constexpr (F6) {
-                dft_tile_max6x2(af, bf[0], bf[1], ny, cm[0], cm[1]);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 2; ++k)
-                    cm[k] = dft_tile_max<VAR>(af, bf[k], ny, false, cm[k]);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            float c = cm[k];
-            if constexpr (HITS) // any hit in the chunk: the first-hit chunk wins
-                c = c >= hl[k] ? __builtin_inff() : c;
-            if (c > best[k]) {
-                best[k] = c;
-                btile[k] = tb;
-            }
-        }
-    };
-    const uint32_t nstage = (wk.w - wk.z + kTilesPerStage - 1) / kTilesPerStage;
-    auto stage_nt = [&](uint32_t st) { return min((uint32_t)kTilesPerStage, wk.w - (wk.z + st * kTilesPerStage)); };
-    if (nstage)
-        stage_tiles<KS, 256, kDftCS>(lds0, a.dtiles, a.dconst, wk.z, stage_nt(0));
-    for (uint32_t st = 0; st < nstage; st += 2) {
-        {
-            const uint32_t tb = wk.z + st * kTilesPerStage;
-            stage_barrier();
-            if (st + 1 < nstage)
-                stage_tiles<KS, 256, kDftCS>(lds1, a.dtiles, a.dconst, tb + kTilesPerStage, stage_nt(st + 1));
-            compute(lds0, stage_nt(st), tb);
-        }
-        if (st + 1 < nstage) {
-            const uint32_t tb = wk.z + (st + 1) * kTilesPerStage;
-            stage_barrier();
-            if (st + 2 < nstage)
-                stage_tiles<KS, 256, kDftCS>(lds0, a.dtiles, a.dconst, tb + kTilesPerStage, stage_nt(st + 2));
-            compute(lds1, stage_nt(st + 1), tb);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-        if (act[k])
-            a.entries[(size_t)(blockIdx.x * kDftBlocksPerWG + 2 * wv + k) * 64 + lane] =
-                make_uint2(__float_as_uint(best[k] * (F6 ? 2.0f : 1.0f)), btile[k]); // F6 tracks h = y/2
 }
 
 // ---------------------------------------------------------------------------
@@ -1585,7 +931,7 @@ __global__ void __launch_bounds__(256, F6 ? 2 : 3) search_dft2(DftArgs d)
 // SORTED (tiles in ΣD4 order, fracenc_tp.hip): rows and tiles are not in domain order, so the
 // least key over every matching row of every tile of the chunk is taken (no first-row shortcut).
 // One slot's least key and the winner's sums (bestk = kKeyNone: padding slot, or no eligible domain).
-// FLIP: the slot holds a T = 8 range's flipped copy (dft_range_prep flip_from), whose rotation t' is the
+// FLIP: the slot holds a T = 8 range's flipped copy (dft_range_prep_pair_at, flip_from), whose rotation t' is the
 // reference's transform 4 + (−t' mod 4); the keys carry the reference's transform and a.T.
 struct DftResolved {
     unsigned long long bestk = kKeyNone;
@@ -1607,7 +953,8 @@ template <bool SORTED>
 __device__ inline DftSlotLoads dft_slot_loads(const MfmaResolveArgs& a, uint32_t slot, int lane)
 {
     DftSlotLoads ld;
-    ld.sb = a.slotbest ? a.slotbest[slot] : 0ull;
+    if constexpr (!SORTED)
+        ld.sb = a.slotbest[slot];
     ld.sa16 = a.rconst[slot];
     const uint4* rp4 = reinterpret_cast<const uint4*>(a.rorb + (size_t)slot * 32 + (lane & 3) * 8);
     ld.r0 = rp4[0];
@@ -1635,13 +982,12 @@ __device__ inline DftResolved resolve_dft_eval(const MfmaResolveArgs& a, uint32_
     const int64_t sa16 = (int64_t)ld.sa16;
     const int i = lane >> 2, g = lane & 3;
     const uint4 r0 = ld.r0, r1 = ld.r1;
-    const uint32_t blk = slot >> 5, col = slot & 31u;
     const uint4 rec0 = ld.rec0, rec1 = ld.rec1;
     const uint2 gw = ld.gw;
     if (ri < 0)
         return res;
-    // lane (i, g) holds orbits 4g..4g+3 of the range as pixel pairs (dft_range_prep) and meets
-    // the same orbits of a domain row (tile-order pool, dft_domain_build). With fwd(t) = g^t,
+    // lane (i, g) holds orbits 4g..4g+3 of the range as pixel pairs (dft_range_prep_pair_at) and meets
+    // the same orbits of a domain row (tile-order pool, dft_domain_build_pair_at). With fwd(t) = g^t,
     //   X_t = Σ_q r(q)·D4(fwd_t q) = Σ_{o,k} r_{o,k}·D_{o,k+t}:
     // t = 0 pairs (A, B) = (D0|D1, D2|D3), t = 2 the swapped pairs (B, A), t = 1 the rotated
     // pairs (D1|D2, D3|D0) = (alignbit(B, A, 16), alignbit(A, B, 16)) and t = 3 those swapped —
@@ -1773,10 +1119,9 @@ __device__ inline DftResolved resolve_dft_eval(const MfmaResolveArgs& a, uint32_
             }
         }
     };
-    if (a.slotbest) {
+    if constexpr (!SORTED) {
         // the search merged its splits itself (search_dft, DftArgs::slotbest): the slot's greatest y, the
-        // earliest chunk attaining it, its tiles to evaluate and which lane halves attain it — one load, no
-        // CSR walk
+        // earliest chunk attaining it, its tiles to evaluate and which lane halves attain it — one load
         if (sb == 0ull)
             return res; // no work item reached the slot: no eligible domain
         vmax = funmap((uint32_t)(sb >> 32));
@@ -1788,9 +1133,9 @@ __device__ inline DftResolved resolve_dft_eval(const MfmaResolveArgs& a, uint32_
         for (uint32_t h = 0; h < 2; ++h)
             if ((hm >> h) & 1u)
                 eval_chunk(tile0, h, tm, a.ntiles);
-    } else if constexpr (SORTED) {
+    } else {
         // the search kept each lane's maximum over its group's window and the chunks attaining it (search_dft
-        // CHUNKED): two loads per slot, no CSR walk.  A block without a group (a bucket without domains) was
+        // CHUNKED): two loads per slot.  A block without a group (a bucket without domains) was
         // never searched and its record is some earlier run's: not read
         if (gw.x == 0xffffffffu)
             return res;
@@ -1816,42 +1161,6 @@ __device__ inline DftResolved resolve_dft_eval(const MfmaResolveArgs& a, uint32_
                 const uint4 wk = a.work[gw.x];
                 for (uint32_t t = wk.z; t < wk.w; t += (uint32_t)kTilesPerStage)
                     eval_chunk(t, h, 0xfu, wk.w);
-            }
-        }
-    } else {
-        const uint32_t e0 = a.blk_ptr[blk], e1 = a.blk_ptr[blk + 1];
-        const uint32_t nent = (e1 - e0) * 2u;
-        // the first 64 entries stay in registers for the ballot walk below
-        uint2 en0 = make_uint2(0u, 0u);
-        for (uint32_t j = lane; j < nent; j += 64) {
-            const uint2 v = a.entries[(size_t)a.blk_ent[e0 + j / 2] * 64 + col + 32 * (j & 1)];
-            if (j < 64)
-                en0 = v;
-            vmax = __builtin_fmaxf(vmax, __uint_as_float(v.x));
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1)
-            vmax = __builtin_fmaxf(vmax, __uint_as_float(lane_xor(__float_as_uint(vmax), lane, o)));
-        vmax = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(vmax))); // wave-uniform
-        if (!(vmax > -1.0e29f))
-            return res; // only padding rows: no eligible domain, best_key stays "none"
-        set_target();
-        const uint32_t vbits = __float_as_uint(vmax);
-        // only the entries holding the maximum are re-evaluated (usually one): the lanes test 64
-        // entries at a time and the wave walks the ballot of matches, so the cost does not grow
-        // with the number of domain splits (many splits per block when ranges are sharded)
-        for (uint32_t c0 = 0; c0 < nent; c0 += 64) {
-            const uint32_t jl = c0 + (uint32_t)lane;
-            const uint2 enl = jl >= nent ? make_uint2(0u, 0u)
-                              : c0 == 0  ? en0
-                                         : a.entries[(size_t)a.blk_ent[e0 + jl / 2] * 64 + col + 32 * (jl & 1)];
-            unsigned long long match = __ballot(jl < nent && enl.x == vbits);
-            while (match) {
-                const int src = __ffsll((long long)match) - 1;
-                match &= match - 1;
-                const uint32_t j = c0 + (uint32_t)src;
-                const uint32_t ey = (uint32_t)__builtin_amdgcn_readlane((int)enl.y, src);
-                eval_chunk(ey, j & 1u, 0xfu, a.ntiles);
             }
         }
     }

@@ -20,10 +20,10 @@ void launch_search_mfma_v(frac_ctx* c, const MfmaSearchArgs& a)
 // wrong results by design, are accepted — and compiled — only by a -DFRAC_TUNING build.
 // Any other value fails the run (FRAC_E_INVALID), so a stray variable cannot corrupt records.
 //   search_mfma: 0..7 schedule bits, 32 s_setprio, 64 late constants, 96, 98, 128 / 130 (default)
-//                the minimum over transforms first; ablations 8, 16
-//   search_dft:  default 8-wave exact form; 1 / 3 four-wave exact / guarded; 5 eight-tile
-//                stages; 6 pairwise-tree row maximum; 12 two range blocks per wave (search_dft2);
-//                ablations 9, 17, 41, 73, 105, 65 (four-wave) and 201..207 (eight-wave)
+//                the minimum over transforms first; 12 and 386; ablations 8, 16
+//   search_dft:  default 35, the guarded six-MFMA form (kDftFastVar); 37 the same always carrying the tile mask;
+//                21 the exact epilogue (kDftExactVar); ablations 240..243 of 35.  The direct form's values
+//                select the default here (dft_variant, fracenc_plan.hip)
 inline int mfma_variant(frac_ctx* c, int& var)
 {
     const char* v = ab_knob("FRAC_MFMA_VARIANT");
@@ -32,9 +32,8 @@ inline int mfma_variant(frac_ctx* c, int& var)
         return FRAC_OK;
     char* end = nullptr;
     const long x = strtol(v, &end, 10);
-    static const int exact[] = {0,  1,  2,  3,  4,  5,  6,  7,  12, 20, 21, 22, 23, 24, 26,
-                                28, 27, 32, 33, 34, 35, 36, 64, 96, 98, 128, 130, 386};
-    static const int ablation[] = {8, 9, 16, 17, 41, 65, 73, 105, 201, 202, 203, 204, 205, 206, 207, 226, 227, 240, 241, 242, 243};
+    static const int exact[] = {0, 1, 2, 3, 4, 5, 6, 7, 12, 21, 32, 35, 37, 64, 96, 98, 128, 130, 386};
+    static const int ablation[] = {8, 16, 240, 241, 242, 243};
     bool ok = end && *end == 0;
     bool known = false;
     for (int e : exact)
@@ -299,13 +298,13 @@ extern "C" int frac_clock_stamps(unsigned long long* out, size_t cap_workgroups)
 #endif
 
 // search_dft with or without the hit test (H = 0: a hit is S16 = 0, which the plain maximum search finds)
-template <int VAR, uint32_t WAVES = 4, uint32_t TPS = kTilesPerStage, bool CHUNKED = false, bool TMASK = false>
+template <int VAR, bool CHUNKED = false, bool TMASK = false>
 void launch_search_dft(frac_ctx* c, const DftArgs& da, unsigned nwg, bool hits)
 {
     if (hits)
-        search_dft<true, VAR, WAVES, TPS, CHUNKED, TMASK><<<nwg, 64 * WAVES, 0, c->stream>>>(da);
+        search_dft<true, VAR, CHUNKED, TMASK><<<nwg, 64 * kDftBlocksPerWG, 0, c->stream>>>(da);
     else
-        search_dft<false, VAR, WAVES, TPS, CHUNKED, TMASK><<<nwg, 64 * WAVES, 0, c->stream>>>(da);
+        search_dft<false, VAR, CHUNKED, TMASK><<<nwg, 64 * kDftBlocksPerWG, 0, c->stream>>>(da);
 }
 
 // n = 8, T = 4: the C4-Fourier search (6 MFMAs per 32×32 tile pair instead of 16).  inits: reset
@@ -327,17 +326,10 @@ inline int launch_dft(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool i
     FRAC_HIP(c, c->d_dft_tpool.ensure((size_t)c->ntiles * 32 * 32));
     const uint32_t nbk = c->nblocks * c->dft_copies; // range blocks incl. T = 8's flipped copies
     FRAC_HIP(c, c->d_dft_rguard.ensure(nbk));
-    // FRAC_MFMA_VARIANT for this path (A/B knob): default = exact form in 8-wave workgroups
-    // with the v_max3-chain row maximum; 20 = the five-MFMA form (kDft5) in the same
-    // workgroups; 6 = the pairwise-tree row maximum; 5 = 8-tile stages; 12 = two range blocks
-    // per wave; 1 = exact form in 4-wave workgroups, 3 = guarded fast path (4 waves), odd
-    // values ≥ 9 = ablations of variant 1 (tuning only: wrong results)
-    int var = 0;
+    int var = 0; // FRAC_MFMA_VARIANT for this path (A/B knob; dft_variant, fracenc_plan.hip)
     FRAC_TRY(mfma_variant(c, var));
     var = dft_variant(var);
-    const int form = dft_form(var);
-    const bool f5 = form != 4; // five domain fragments per tile (forms 5 and 6)
-    FRAC_HIP(c, c->d_m_dtiles.ensure((size_t)c->ntiles * (f5 ? 5 : 4) * 64));
+    FRAC_HIP(c, c->d_m_dtiles.ensure((size_t)c->ntiles * kDftKS * 64));
     d.dtiles = c->d_m_dtiles.ptr;
     DftDomainBuildArgs b;
     b.src = c->d_src.ptr;
@@ -361,11 +353,9 @@ inline int launch_dft(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool i
     FRAC_HIP(c, c->d_dft_rorb.ensure((size_t)r.nblocks * 32 * 32));
     r.rorb = c->d_dft_rorb.ptr;
     // the search merges its domain splits per slot (64-bit atomicMax; reset by the range prep), so the resolve
-    // reads one word per slot instead of walking the block's entries through the CSR map
-    // (search_dft2, an A/B form of the tuning build, writes entries only)
-    const bool slotbest = !(kTuningBuild && ((form == 6 && var == 23) || (!dft_four_wave(var) && var == 12)));
+    // reads one word per slot: no per-work-item entries, no CSR map
     FRAC_HIP(c, c->d_dft_slotbest.ensure((size_t)r.nblocks * 32));
-    r.slotbest = slotbest ? c->d_dft_slotbest.ptr : nullptr;
+    r.slotbest = c->d_dft_slotbest.ptr;
     // one launch: domain tiles, range blocks and (inits) the run's resets
     DftPrepInit in;
     if (inits) {
@@ -378,30 +368,22 @@ inline int launch_dft(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool i
     in.plan = c->qplan;
     in.copies = c->dft_copies;
     const unsigned pg = in.dblocks + (nbk * 64 + 255) / 256; // two lanes per range slot (dft_range_prep_pair_at)
-    if (pg || inits) {
-        int32_t* trmax = f5 ? c->d_dft_trmax.ptr : nullptr;
-        const dim3 grid(std::max(pg, 1u));
-        if (form == 5)
-            dft_prep<5><<<grid, 256, 0, c->stream>>>(d, b, c->d_dft_tguard.ptr, trmax, r, c->d_dft_rguard.ptr, in);
-        else if (form == 6)
-            dft_prep<6><<<grid, 256, 0, c->stream>>>(d, b, c->d_dft_tguard.ptr, trmax, r, c->d_dft_rguard.ptr, in);
-        else
-            dft_prep<4><<<grid, 256, 0, c->stream>>>(d, b, c->d_dft_tguard.ptr, trmax, r, c->d_dft_rguard.ptr, in);
-    }
+    if (pg || inits)
+        dft_prep<<<std::max(pg, 1u), 256, 0, c->stream>>>(d, b, c->d_dft_tguard.ptr, c->d_dft_trmax.ptr, r,
+                                                         c->d_dft_rguard.ptr, in);
     if ((c->p.flags & FRAC_FLAG_TIMING) && mark_prep)
         FRAC_TRY(mark_event(c, 1));
-    const bool four = dft_four_wave(var);
-    const std::vector<uint4>& work = four ? c->m_work : c->m8_work;
+    const std::vector<uint4>& work = c->m8_work;
     c->form_ran = FRAC_FORM_FOURIER;
     c->flops_ran = 0;
-    for (const uint4& w : work) // 8 (forms 5 / 6: 5 / 6) MFMA 32x32x16 (32768 flops each) per (block, tile)
-        c->flops_ran += (uint64_t)w.y * (w.w - w.z) * (form == 5 ? 5ull : form == 6 ? 6ull : 8ull) * 32768ull;
+    for (const uint4& w : work) // 6 MFMA 32x32x16 (32768 flops each) per (block, tile)
+        c->flops_ran += (uint64_t)w.y * (w.w - w.z) * 6ull * 32768ull;
     const uint32_t nwork = launch_nwork(c, work);
     if (nwork) {
         DftArgs da;
-        da.m = search_args(c, four ? c->d_m_work.ptr : c->d_m8_work.ptr, nwork);
+        da.m = search_args(c, c->d_m8_work.ptr, nwork);
+        da.m.entries = nullptr; // (the direct form's: search_dft merges per slot)
         da.rguard = c->d_dft_rguard.ptr;
-        da.tguard = c->d_dft_tguard.ptr;
         da.trmax = c->d_dft_trmax.ptr;
         da.slotbest = r.slotbest;
         const unsigned nwg = nwork;
@@ -409,128 +391,35 @@ inline int launch_dft(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool i
         da.stamps = clock_stamps_for(nwg);
 #endif
         const bool hits = c->hitH > 0;
-        constexpr uint32_t W8 = kDftBlocksPerWG;
 #ifndef FRAC_TUNING
         // the product build: the shipped form only (variant 35, kDftDefaultVariant) — the six-MFMA
         // form with the guarded constant-folded epilogue, the unrolled chunk and buffer_load … lds stages
         static_assert(kDftDefaultVariant == 35, "the product build's Fourier search is variant 35");
-        (void)four;
-        constexpr int V35 = 1 | kDftChain | kDft6 | kDftFast6 | kDftUnroll | kDftBufDma;
         // few tiles: the run is a short chain whose resolve weighs as much as its search, and the search also
         // carries the tiles of the winning chunk that attain its maximum (TMASK) so the resolve evaluates those
         if (c->ntiles <= kDftTmaskTiles)
-            launch_search_dft<V35, W8, kTilesPerStage, false, true>(c, da, nwg, hits);
+            launch_search_dft<kDftFastVar, false, true>(c, da, nwg, hits);
         else
-            launch_search_dft<V35, W8>(c, da, nwg, hits);
-#else // the tuning build: every A/B variant and ablation
-        if (form == 6 && var == 37) { // variant 35 carrying the winning chunk's tile mask (TMASK)
-            constexpr int V35 = 1 | kDftChain | kDft6 | kDftFast6 | kDftUnroll | kDftBufDma;
-            launch_search_dft<V35, W8, kTilesPerStage, false, true>(c, da, nwg, hits);
-        } else if (!four && var >= 200) {
-            // ablations of the 8-wave exact form (wrong results by design)
-            switch (var) {
-            case 201: search_dft<false, 9, W8><<<nwg, 64 * W8, 0, c->stream>>>(da); break;   // MFMA-only
-            case 202: search_dft<false, 73, W8><<<nwg, 64 * W8, 0, c->stream>>>(da); break;  // MFMA-only, no DMA/bar
-            case 203: search_dft<false, 265, W8><<<nwg, 64 * W8, 0, c->stream>>>(da); break; // MFMA-only, no DMA
-            case 204: search_dft<false, 521, W8><<<nwg, 64 * W8, 0, c->stream>>>(da); break; // MFMA-only, no barrier
-            case 205: search_dft<false, 257, W8><<<nwg, 64 * W8, 0, c->stream>>>(da); break; // full, no DMA
-            case 206: search_dft<false, 513, W8><<<nwg, 64 * W8, 0, c->stream>>>(da); break; // full, no barrier
-            case 226: // the guarded six-MFMA form (26), no barrier
-                search_dft<false, 1 | kDftChain | kDft6 | kDftFast6 | 512, W8><<<nwg, 64 * W8, 0, c->stream>>>(da);
-                break;
-            case 227: // the guarded six-MFMA form (26), no LDS-DMA / barrier after the first stages
-                search_dft<false, 1 | kDftChain | kDft6 | kDftFast6 | 64, W8><<<nwg, 64 * W8, 0, c->stream>>>(da);
-                break;
-            case 240: // variant 35, MFMAs with a one-value epilogue
-                search_dft<false, 1 | kDftChain | kDft6 | kDftFast6 | kDftUnroll | kDftBufDma | 8, W8><<<nwg, 64 * W8, 0,
-                                                                                                    c->stream>>>(da);
-                break;
-            case 241: // variant 35, the fast epilogue without MFMAs
-                search_dft<false, 1 | kDftChain | kDft6 | kDftFast6 | kDftUnroll | kDftBufDma | 16, W8><<<nwg, 64 * W8, 0,
-                                                                                                     c->stream>>>(da);
-                break;
-            case 242: // variant 35, no barrier
-                search_dft<false, 1 | kDftChain | kDft6 | kDftFast6 | kDftUnroll | kDftBufDma | 512, W8><<<nwg, 64 * W8,
-                                                                                                      0, c->stream>>>(da);
-                break;
-            case 243: // variant 35, no LDS-DMA / barrier after the first stages
-                search_dft<false, 1 | kDftChain | kDft6 | kDftFast6 | kDftUnroll | kDftBufDma | 64, W8><<<nwg, 64 * W8, 0,
-                                                                                                     c->stream>>>(da);
-                break;
-            default: search_dft<false, 65, W8><<<nwg, 64 * W8, 0, c->stream>>>(da); break;  // full, no DMA/bar
-            }
-        } else if (form == 6 && var == 23) { // the six-MFMA form, two range blocks per wave (search_dft2)
-            if (hits)
-                search_dft2<true, true><<<nwg, 256, 0, c->stream>>>(da);
-            else
-                search_dft2<false, true><<<nwg, 256, 0, c->stream>>>(da);
-        } else if (form == 6 && (var == 27 || var == 28)) { // 16 range blocks per (1024-thread) workgroup
-            if (c->m8_bpw != 16)
-                return c->fail(FRAC_E_STATE, "search_dft: work lists built for another workgroup size");
-            if (var == 27) {
-                launch_search_dft<1 | kDftChain | kDft6, 16>(c, da, nwg, hits);
-            } else {
-                launch_search_dft<1 | kDftChain | kDft6 | kDftFast6, 16>(c, da, nwg, hits);
-            }
-        } else if (form == 6 && var >= 33 && var <= 36) { // 26 with the issue-cost knobs
-            constexpr int V = 1 | kDftChain | kDft6 | kDftFast6;
-            switch (var) {
-            case 33: // unrolled chunk
-                launch_search_dft<V | kDftUnroll, W8>(c, da, nwg, hits);
-                break;
-            case 34: // buffer_load … lds stages
-                launch_search_dft<V | kDftBufDma, W8>(c, da, nwg, hits);
-                break;
-            case 35: // both
-                launch_search_dft<V | kDftUnroll | kDftBufDma, W8>(c, da, nwg, hits);
-                break;
-            default: // both, second half of the waves at s_setprio 1
-                launch_search_dft<V | kDftUnroll | kDftBufDma | kDftPrio, W8>(c, da, nwg, hits);
-                break;
-            }
-        } else if (form == 6 && var == 26) { // the six-MFMA form, guarded constant-folded epilogue
-            launch_search_dft<1 | kDftChain | kDft6 | kDftFast6, W8>(c, da, nwg, hits);
-        } else if (form == 6) { // the six-MFMA form
-            launch_search_dft<1 | kDftChain | kDft6, W8>(c, da, nwg, hits);
-        } else if (var == 22) { // the five-MFMA form, unpacked epilogue
-            launch_search_dft<1 | kDftChain | kDft5 | kDftScalar, W8>(c, da, nwg, hits);
-        } else if (form == 5) { // the five-MFMA form
-            launch_search_dft<1 | kDftChain | kDft5, W8>(c, da, nwg, hits);
-        } else if (!four && var == 5) { // 8-tile LDS stages
-            launch_search_dft<1 | kDftChain, W8, 8>(c, da, nwg, hits);
-        } else if (!four && var == 12) { // two range blocks per wave (4-wave workgroups, the 8-block lists)
-            static_assert(kDftBlocksPerWG == 8, "search_dft2 covers 8 blocks per workgroup");
-            if (hits)
-                search_dft2<true><<<nwg, 256, 0, c->stream>>>(da);
-            else
-                search_dft2<false><<<nwg, 256, 0, c->stream>>>(da);
-        } else if (!four && var == 6) { // the pairwise-tree row maximum (round 1's default, A/B)
-            launch_search_dft<1, W8>(c, da, nwg, hits);
-        } else if (!four) {
-            launch_search_dft<1 | kDftChain, W8>(c, da, nwg, hits);
-        } else if (var == 1) {
-            launch_search_dft<1>(c, da, nwg, hits);
-        } else if (var == 3) {
-            launch_search_dft<0>(c, da, nwg, hits);
-        } else {
-            // ablations of the 4-wave exact form (wrong results by design)
-            switch (var) {
-            case 9: search_dft<false, 9><<<nwg, 256, 0, c->stream>>>(da); break;     // MFMA-only
-            case 17: search_dft<false, 17><<<nwg, 256, 0, c->stream>>>(da); break;   // VALU-only
-            case 41: search_dft<false, 41><<<nwg, 256, 0, c->stream>>>(da); break;   // MFMA-only, no LDS reads
-            case 73: search_dft<false, 73><<<nwg, 256, 0, c->stream>>>(da); break;   // MFMA-only, no DMA/barrier
-            case 105: search_dft<false, 105><<<nwg, 256, 0, c->stream>>>(da); break; // MFMA-only, neither
-            case 65: search_dft<false, 65><<<nwg, 256, 0, c->stream>>>(da); break;   // full, no DMA/barrier
-            default: search_dft<false, 1><<<nwg, 256, 0, c->stream>>>(da); break;
-            }
+            launch_search_dft<kDftFastVar>(c, da, nwg, hits);
+#else // the tuning build: the shipped form, its A/B partners and its ablations (wrong results by design)
+        constexpr unsigned kThreads = 64 * kDftBlocksPerWG;
+        switch (var) {
+        case 37: launch_search_dft<kDftFastVar, false, true>(c, da, nwg, hits); break; // 35 carrying the tile mask
+        case 21: launch_search_dft<kDftExactVar>(c, da, nwg, hits); break;              // the exact epilogue
+        case 240: search_dft<false, kDftFastVar | 8><<<nwg, kThreads, 0, c->stream>>>(da); break;   // MFMAs, one-value epilogue
+        case 241: search_dft<false, kDftFastVar | 16><<<nwg, kThreads, 0, c->stream>>>(da); break;  // the fast epilogue, no MFMA
+        case 242: search_dft<false, kDftFastVar | 512><<<nwg, kThreads, 0, c->stream>>>(da); break; // no barrier
+        case 243: search_dft<false, kDftFastVar | 64><<<nwg, kThreads, 0, c->stream>>>(da); break;  // no LDS-DMA / barrier
+                                                                                                   // after the first stages
+        default: launch_search_dft<kDftFastVar>(c, da, nwg, hits); break; // 35
         }
 #endif
     }
     if (c->p.flags & FRAC_FLAG_TIMING)
         FRAC_TRY(mark_event(c, 2));
     if (nr) {
-        MfmaResolveArgs v = resolve_args(c, dtgt, tstride, nr, four ? c->d_m_blk_ptr.ptr : c->d_m8_blk_ptr.ptr,
-                                         four ? c->d_m_blk_ent.ptr : c->d_m8_blk_ent.ptr);
+        MfmaResolveArgs v = resolve_args(c, dtgt, tstride, nr, nullptr, nullptr); // no CSR map, no entries
+        v.entries = nullptr;
         v.T = c->dft_copies == 2 ? 8u : 4u;
         v.slot_range = c->d_m_slot_range.ptr;
         v.nslots = c->nblocks * 32u;
@@ -815,15 +704,13 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
             FRAC_TRY(mark_event(c, 2));
         return FRAC_OK;
     }
-    constexpr uint32_t W8 = kDftBlocksPerWG;
     DftArgs da;
     da.m = search_args(c, c->d_tp_work.ptr, ng); // (host-planned only: no plan)
     da.rguard = c->d_dft_rguard.ptr;
-    da.tguard = c->d_dft_tguard.ptr;
     da.trmax = nullptr; // the seed search runs the exact epilogue (kTpSeedVar); the windowed search's below
     // seed: the Fourier search over one tile per group, into the records the windowed search writes again
     da.rec = c->d_tp_rec.ptr;
-    search_dft<false, kTpSeedVar, W8, 4, true><<<ng, 64 * W8, 0, c->stream>>>(da);
+    search_dft<false, kTpSeedVar, true><<<ng, 64 * kDftBlocksPerWG, 0, c->stream>>>(da);
     // per group: its blocks' seed bounds, then its window
     TpWindowArgs w;
     w.groups = c->d_tp_groups.ptr;
@@ -854,7 +741,7 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
     const uint64_t pairs = (uint64_t)tot[2] | ((uint64_t)tot[3] << 32);
     if (budgeted) {
         // the seed search is issued work on either route: one tile per block, the tiled form's MFMAs
-        const uint64_t seed_flops = c->tp_seed_pairs * (kDftTpForm == 6 ? 6ull : 8ull) * 32768ull;
+        const uint64_t seed_flops = c->tp_seed_pairs * 6ull * 32768ull;
         const uint64_t seed_evals = (uint64_t)tot[6] | ((uint64_t)tot[7] << 32);
         if (pairs * kAutoPruneBudgetDen > c->tp_full_pairs * kAutoPruneBudgetNum) {
             if (getenv("FRAC_TRACE"))
@@ -872,11 +759,11 @@ int launch_tp(frac_ctx* c, const uint8_t* dtgt, uint32_t tstride, bool timing, b
     }
     // issued matrix work (8 MFMA 32×32×16 per block × tile) and the (range, domain) pairs in the windows
     // (padding slots and rows of partial blocks and tiles are no pairs)
-    c->flops_ran += pairs * (kDftTpForm == 6 ? 6ull : 8ull) * 32768ull;
+    c->flops_ran += pairs * 6ull * 32768ull;
     c->evaluated_ran += (uint64_t)tot[4] | ((uint64_t)tot[5] << 32);
     da.trmax = kTpFast ? c->d_dft_trmax.ptr : nullptr;
     da.order = kTpLongestFirst ? c->d_tp_order.ptr : nullptr; // the longest windows first (tp_plan)
-    launch_search_dft<kTpVar, W8, 4, true>(c, da, ng, c->hitH > 0);
+    launch_search_dft<kTpVar, true>(c, da, ng, c->hitH > 0);
     if (timing)
         FRAC_TRY(mark_event(c, 2));
     MfmaResolveArgs v = resolve_args(c, dtgt, tstride, nr, nullptr, nullptr); // (records, no CSR map)
@@ -1102,7 +989,7 @@ int launch_all(frac_ctx* c)
         FRAC_HIP(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_fb_count.ptr), (int)fbc, 1, c->stream));
     }
     // the Fourier path and the SEA engine's tiled form build the pool in their fused domain pass
-    // (dft_domain_build)
+    // (dft_domain_build_pair_at)
     // (and the direct form at n = 4 / 16 in mfma_prep's domain half)
     const bool fused_pool = !c->virt &&
                             ((N == 8 && ((use_mfma && (c->p.transforms == 4 || c->dft_copies == 2) && mfma_dft_enabled(c)) ||

@@ -260,13 +260,13 @@ struct MfmaRangePrepArgs {
     uint32_t T;
     uint4* rfrags;             // [nblocks][T][KS][64]
     uint32_t* rconst;          // [nblocks*32]
-    uint32_t* rorb = nullptr;  // dft_range_prep: [nblocks*32][32] pixel pairs in orbit order (resolve_dft)
-    uint32_t flip_from = ~0u;  // dft_range_prep: blocks from here on hold their range read through Flip (T = 8)
+    uint32_t* rorb = nullptr;  // dft_range_prep_pair_at: [nblocks*32][32] pixel pairs in orbit order (resolve_dft)
+    uint32_t flip_from = ~0u;  // dft_range_prep_pair_at: blocks from here on hold their range read through Flip (T = 8)
     const DevPlan* plan = nullptr; // device-planned search: the block count (and flip_from) from the plan
     int fmode = 0;             // mfma_range_prep, the float-C epilogue: B = 8·(128 − copy_t)
-    unsigned long long* slotbest = nullptr; // dft_range_prep / mfma_range_prep: [nblocks*32] reset to 0 (the
+    unsigned long long* slotbest = nullptr; // dft_prep / mfma_range_prep: [nblocks*32] reset to 0 (the
                                             // searches' merged slot words)
-    const uint8_t* rpix = nullptr; // dft_range_prep_pair_at<…, RPIX>: [nr][64] the ranges' pixels in range order
+    const uint8_t* rpix = nullptr; // dft_range_prep_pair_at<RPIX>: [nr][64] the ranges' pixels in range order
 };
 
 // the range-block count of a device-planned search (T = 8 Fourier: the originals and their copies)
@@ -944,11 +944,11 @@ struct MfmaResolveArgs {
     uint32_t T;
     int64_t hitH;               // −1: no hits
     unsigned long long* best_key;
-    // resolve_dft only: waves walk the slots; D4 rows in tile order (dft_domain_build)
+    // resolve_dft only: waves walk the slots; D4 rows in tile order (dft_domain_build_pair_at)
     const int32_t* slot_range;  // [nslots] range of each slot, −1 padding
     uint32_t nslots;
-    const uint32_t* tpool;      // [ntiles*32][32] D4 pairs in orbit order (dft_domain_build)
-    const uint32_t* rorb;       // [nslots][32] range pixel pairs in orbit order (dft_range_prep)
+    const uint32_t* tpool;      // [ntiles*32][32] D4 pairs in orbit order (dft_domain_build_pair_at)
+    const uint32_t* rorb;       // [nslots][32] range pixel pairs in orbit order (dft_range_prep_pair_at)
     uint4* rstat = nullptr;     // [nr] the winner's {X_t, ΣD4 | Σr << 16, ΣD4², Σr²} (fit_rstat)
     uint32_t flip_slots = 0;    // T = 8 Fourier: slot s's flipped copy is slot s + flip_slots (0: none)
     int merged = 0;             // resolve_mfma: entries hold the minimum over every transform (search_mfma VAR 128)

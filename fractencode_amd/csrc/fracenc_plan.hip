@@ -109,22 +109,11 @@ int device_buckets(frac_ctx* c, int nb, uint32_t* dfirst, uint32_t* rfirst)
 
 inline int mfma_variant(frac_ctx* c, int& var);
 inline bool mfma_dft_enabled(const frac_ctx* c);
-// the Fourier search variants that run 4-wave workgroups (and read m_work): 1, 3 and the odd
-// ablations below 200; every other variant runs 8-wave workgroups on m8_work
-// the variants that run search_dft in 4-wave workgroups over the 4-block work lists: 1, 3 and the
-// tuning ablations of 1 (the other odd A/B values, e.g. 21, are 8-block forms)
-inline bool dft_four_wave(int var)
-{
-    return var == 1 || var == 3 || var == 9 || var == 17 || var == 41 || var == 65 || var == 73 || var == 105;
-}
-// the Fourier form's domain/range fragment layout: 4 (8 MFMA per tile pair), 5 (kDft5, variants 20, 22),
-// 6 (kDft6, variants 21, 23)
 // the SEA tiled form's search_dft: the seed search (one tile per group) keeps the exact epilogue; the windowed
-// search runs the exhaustive search's tuned variant (35: kDftFast6 | kDftUnroll | kDftBufDma) when kTpFastSearch
-constexpr int kTpSeedVar = 1 | kDftChain | (kDftTpForm == 6 ? kDft6 : 0);
-constexpr bool kTpFast = kTpFastSearch && kDftTpForm == 6;
-constexpr int kTpVar = kTpFast ? (kTpSeedVar | kDftFast6 | kDftUnroll | kDftBufDma) : kTpSeedVar;
-constexpr uint32_t kTpKS = kDftTpForm == 4 ? 4u : 5u;                    // its domain fragments per tile
+// search runs the exhaustive search's shipped form (variant 35) when kTpFastSearch
+constexpr int kTpSeedVar = kDftExactVar;
+constexpr bool kTpFast = kTpFastSearch;
+constexpr int kTpVar = kTpFast ? kDftFastVar : kTpSeedVar;
 // FRAC_ENGINE_AUTO's pruned route (n = 8, T = 4, ratio 2; DESIGN §4.4, measured in §7.4).
 // kAutoPruneMinPairs: the fewest block × tile pairs (every window open) at which AUTO tries the bound; below
 // it the route's fixed cost — the two sides' sort, about ten small launches, one host turnaround — is too large a
@@ -140,38 +129,24 @@ constexpr uint32_t kTpKS = kDftTpForm == 4 ? 4u : 5u;                    // its 
 // a share of 0.43, rounded down to 3/8.
 constexpr uint64_t kAutoPruneMinPairs = 16000000;
 constexpr uint64_t kAutoPruneBudgetNum = 3, kAutoPruneBudgetDen = 8;
-inline int dft_form(int var)
-{
-    if (var == 20 || var == 22)
-        return 5;
-    const bool six = var == 21 || var == 23 || (var >= 26 && var <= 28) || (var >= 33 && var <= 37) ||
-                     var == 226 || var == 227 || (var >= 240 && var <= 243);
-    return six ? 6 : 4;
-}
-// range blocks (waves) per workgroup of the Fourier search: 16 for variants 27 / 28 (1024-thread
-// workgroups: each LDS stage serves twice the blocks, half the LDS-DMA per tile pair), else 8
-inline uint32_t dft_bpw(int var) { return var == 27 || var == 28 ? 16u : kDftBlocksPerWG; }
-// The Fourier path's own variants: 1, 3 (4-wave exact / guarded), 5 (8-tile stages), 6 (pairwise-tree
-// row maximum), 12 (two range blocks per wave), 20 / 22 (five-MFMA form, packed / plain epilogue),
-// 21 / 23 (six-MFMA form, one / two range blocks per wave), 24 (the 8-MFMA exact form in 8-wave
-// workgroups), 26 (the six-MFMA form with the guarded constant-folded epilogue, kDftFast6) and the
-// tuning ablations.  Every other value (the default, and the direct form's
-// schedule knobs) runs kDftDefaultVariant.
-// the six-MFMA form with the guarded constant-folded epilogue, the chunk unrolled and wave-uniform
-// buffer_load … lds stages (variant 35): 12.09 / 12.02 vs 13.85 / 13.65 ms for the exact six-MFMA
-// form (21) at C3 in two 8-round interleaved A/Bs on two boxes (profiles/r03/session3/r03_ab5.log,
-// r03_ab6.log); 21 was 13.71 vs 15.23 ms for the 8-MFMA form (24) in round 2
+// FRAC_MFMA_VARIANT on the Fourier path, in a tuning build: 35 (the default: the six-MFMA form with the guarded
+// constant-folded epilogue, the chunk unrolled and wave-uniform buffer_load … lds stages, kDftFastVar), 37 (35
+// always carrying the winning chunk's tile mask, TMASK), 21 (the exact epilogue, kDftExactVar: the A/B of the
+// guard) and 240–243 (ablations of 35).  Every other value (the direct form's schedule knobs) runs the default.
+// 35 against 21: 12.09 / 12.02 vs 13.85 / 13.65 ms at C3 in two 8-round interleaved A/Bs on two boxes
+// (profiles/r03/session3/r03_ab5.log, r03_ab6.log); the forms retired since — the 8- and five-MFMA forms, two
+// blocks per wave, 4- and 16-wave workgroups, 8-tile stages — are measured in DESIGN §7.2.
 constexpr int kDftDefaultVariant = 35;
 // up to this many domain tiles the product build's search also carries the winning chunk's tile mask
 // (search_dft TMASK; the tuning build's variant 37 always does)
 constexpr uint32_t kDftTmaskTiles = 1024;
 inline int dft_variant(int var)
 {
-    static const int own[] = {1, 3, 5, 6, 12, 20, 21, 22, 23, 24, 26, 27, 28, 33, 34, 35, 36, 37, 9, 17, 41, 65, 73, 105};
+    static const int own[] = {21, 35, 37, 240, 241, 242, 243};
     for (int v : own)
         if (var == v)
             return var;
-    return var >= 200 ? var : kDftDefaultVariant;
+    return kDftDefaultVariant;
 }
 
 // Domain items as the search needs them: one size (Size32u, rectangles allowed), at least 2×2 (the
@@ -512,12 +487,13 @@ struct MfmaBuckets {
     uint32_t nblocks = 0; // range blocks of one copy
 };
 
-// work items: groups of up to BPW blocks of one bucket × splits of its tiles, plus the
-// CSR map block → entry bases (work·BPW + wave) the resolve kernels read
+// work items: groups of up to BPW blocks of one bucket × splits of its tiles, plus, when asked for (blk_ptr and
+// blk_ent not null: the direct form), the CSR map block → entry bases (work·BPW + wave) its resolve kernels read
 // (copies: 2 with T = 8's flipped range blocks on the Fourier path, else 1)
 void build_work(const MfmaBuckets& mb, uint32_t copies, uint32_t bpw, size_t target_wgs, std::vector<uint4>& work,
-                std::vector<uint32_t>& blk_ptr, std::vector<uint32_t>& blk_ent, bool xcd_order)
+                std::vector<uint32_t>* blk_ptr, std::vector<uint32_t>* blk_ent, bool xcd_order)
 {
+    const bool csr = blk_ptr && blk_ent;
     const int nb = (int)mb.blk_count.size();
     const auto &blk_first = mb.blk_first, &blk_count = mb.blk_count, &tile_first = mb.tile_first,
                &tile_count = mb.tile_count;
@@ -534,7 +510,8 @@ void build_work(const MfmaBuckets& mb, uint32_t copies, uint32_t bpw, size_t tar
     // sized by a count pass, then filled in work order (no per-block lists)
     const uint32_t ncp = copies, nbt = mb.nblocks * ncp; // T = 8 Fourier: flipped copies
     std::vector<uint32_t> nsplit(nb, 0);
-    blk_ptr.assign(nbt + 1, 0);
+    if (csr)
+        blk_ptr->assign(nbt + 1, 0);
     for (int b = 0; b < nb; ++b) {
         if (!tile_count[b] || !blk_count[b])
             continue;
@@ -545,14 +522,18 @@ void build_work(const MfmaBuckets& mb, uint32_t copies, uint32_t bpw, size_t tar
         for (size_t sp = 0; sp < splits; ++sp)
             ns += (uint64_t)tile_count[b] * (sp + 1) / splits > (uint64_t)tile_count[b] * sp / splits;
         nsplit[b] = (uint32_t)splits;
-        for (uint32_t cp = 0; cp < ncp; ++cp)
-            for (uint32_t k = 0; k < blk_count[b]; ++k)
-                blk_ptr[cp * mb.nblocks + blk_first[b] + k + 1] = ns;
+        if (csr)
+            for (uint32_t cp = 0; cp < ncp; ++cp)
+                for (uint32_t k = 0; k < blk_count[b]; ++k)
+                    (*blk_ptr)[cp * mb.nblocks + blk_first[b] + k + 1] = ns;
     }
-    for (uint32_t b = 0; b < nbt; ++b)
-        blk_ptr[b + 1] += blk_ptr[b];
-    blk_ent.assign(blk_ptr[nbt], 0);
-    std::vector<uint32_t> cur(blk_ptr.begin(), blk_ptr.end() - 1);
+    std::vector<uint32_t> cur;
+    if (csr) {
+        for (uint32_t b = 0; b < nbt; ++b)
+            (*blk_ptr)[b + 1] += (*blk_ptr)[b];
+        blk_ent->assign((*blk_ptr)[nbt], 0);
+        cur.assign(blk_ptr->begin(), blk_ptr->end() - 1);
+    }
     work.clear();
     for (uint32_t cp = 0; cp < ncp; ++cp)
         for (int b = 0; b < nb; ++b) {
@@ -570,8 +551,9 @@ void build_work(const MfmaBuckets& mb, uint32_t copies, uint32_t bpw, size_t tar
                     const uint32_t w = (uint32_t)work.size();
                     work.push_back(make_uint4(bf + g, nbk, t0, t1));
                     split_of.push_back((uint32_t)sp);
-                    for (uint32_t k = 0; k < nbk; ++k)
-                        blk_ent[cur[bf + g + k]++] = w * bpw + k;
+                    if (csr)
+                        for (uint32_t k = 0; k < nbk; ++k)
+                            (*blk_ent)[cur[bf + g + k]++] = w * bpw + k;
                 }
             }
         }
@@ -622,8 +604,9 @@ void build_work(const MfmaBuckets& mb, uint32_t copies, uint32_t bpw, size_t tar
             inv[order[n]] = n;
         }
         work.swap(nw);
-        for (uint32_t& e : blk_ent)
-            e = inv[e / bpw] * bpw + e % bpw;
+        if (csr)
+            for (uint32_t& e : *blk_ent)
+                e = inv[e / bpw] * bpw + e % bpw;
     }
 }
 
@@ -656,32 +639,29 @@ int plan_mfma_work(frac_ctx* c, const PrepBuckets& B)
     }
     const bool fourier = n == 8 && (T == 4 || T == 8) && !c->virt && mfma_dft_enabled(c);
     c->dft_copies = fourier && T == 8 ? 2u : 1u;
-    int var = 0;
+    int var = 0; // (only checked here: a bad FRAC_MFMA_VARIANT fails the preparation, not the first run)
     FRAC_TRY(mfma_variant(c, var));
-    const bool four_wave = dft_four_wave(var);
     if (n == 16) // search_mfma16: mfma16_bpw(T) range blocks per 4-wave workgroup (Teff: 1 when sampled)
-        build_work(mb, c->dft_copies, mfma16_bpw(c->Teff), kMfma16TargetWgs, c->m_work, c->m_blk_ptr, c->m_blk_ent,
+        build_work(mb, c->dft_copies, mfma16_bpw(c->Teff), kMfma16TargetWgs, c->m_work, &c->m_blk_ptr, &c->m_blk_ent,
                    false);
-    else if (!fourier || four_wave) // the 8-wave Fourier search reads only its own list
-        build_work(mb, c->dft_copies, 4, 8192, c->m_work, c->m_blk_ptr, c->m_blk_ent, false);
+    else if (!fourier) // the Fourier search reads only its own list
+        build_work(mb, c->dft_copies, 4, 8192, c->m_work, &c->m_blk_ptr, &c->m_blk_ent, false);
     else {
         c->m_work.clear();
         c->m_blk_ptr.assign(c->nblocks + 1, 0);
         c->m_blk_ent.clear();
     }
-    if (n == 8 && !c->virt && (T == 4 || c->dft_copies == 2)) {
+    c->m8_built = n == 8 && !c->virt && (T == 4 || c->dft_copies == 2);
+    if (c->m8_built) {
         // FRAC_DFT_WGS (tuning knob): target workgroup count of the Fourier search
         const char* tw = ab_knob("FRAC_DFT_WGS");
-        c->m8_bpw = dft_bpw(dft_variant(var));
-        const size_t wgs = tw ? (size_t)std::max(1, atoi(tw)) : 8192 / c->m8_bpw * 4;
+        const size_t wgs = tw ? (size_t)std::max(1, atoi(tw)) : 8192 / kDftBlocksPerWG * 4;
         // FRAC_XCD_ORDER (tuning knob): 0 = work items in (block group, split) order
         const char* xo = ab_knob("FRAC_XCD_ORDER");
-        build_work(mb, c->dft_copies, c->m8_bpw, wgs, c->m8_work, c->m8_blk_ptr, c->m8_blk_ent,
-                   xo ? atoi(xo) != 0 : true);
+        // (no CSR map: the search merges its splits per slot itself, DftArgs::slotbest)
+        build_work(mb, c->dft_copies, kDftBlocksPerWG, wgs, c->m8_work, nullptr, nullptr, xo ? atoi(xo) != 0 : true);
     } else {
         c->m8_work.clear();
-        c->m8_blk_ptr.clear();
-        c->m8_blk_ent.clear();
     }
     return FRAC_OK;
 }
@@ -759,12 +739,12 @@ int fill_tp(frac_ctx* c, const PrepBuckets& B)
     // The tiled form's layout is ΣD4-sorted tiles and ΣR-sorted blocks, rebuilt every run; the MFMA route's is
     // the domain and range order, filled once (fill_mfma).  Under AUTO both stay prepared, so per buffer:
     //   own copy per layout — the maps and lists the MFMA route fills at prepare() and never again: tile_pos,
-    //     slot_range / range_slot, the 8-block work list (d_tp_* here), and the exhaustive route's block → entry
-    //     CSR map (d_m_* / d_m8_*; the tiled form has none: its search leaves one record per block and lane,
-    //     d_tp_rec).  Small: 4 bytes per tile row, slot and range, 16 per record.
+    //     slot_range / range_slot, the 8-block work list (d_tp_* here; d_tp_rec, the tiled form's one record
+    //     per block and lane, where the exhaustive route has its slot words).  Small: 4 bytes per tile row, slot
+    //     and range, 16 per record.
     //   shared, rebuilt by whichever search runs — everything a run derives from the frame: the tile fragments
     //     and constants (d_m_dtiles, d_m_dconst), the guards, the tile-order pool copy (d_dft_tpool), the range
-    //     fragments, constants and orbit copies (d_m_rfrags, d_m_rconst, d_dft_rorb) and d_m_entries.  dft_prep
+    //     fragments, constants and orbit copies (d_m_rfrags, d_m_rconst, d_dft_rorb).  dft_prep
     //     writes every row of each, padding rows included, from its own maps (the exhaustive route needs that
     //     frame after frame anyway), so a fallback reads nothing the abandoned attempt laid out.  The pool and
     //     −ΣD4² are indexed by pool position in both layouts (the tiled form writes them in tp_keys, before its
@@ -772,9 +752,9 @@ int fill_tp(frac_ctx* c, const PrepBuckets& B)
     FRAC_HIP(c, c->d_tp_slot_range.ensure(nbk * 32));
     FRAC_HIP(c, c->d_tp_range_slot.ensure(nr));
     FRAC_HIP(c, c->d_tp_tile_pos.ensure(nt * 32));
-    FRAC_HIP(c, c->d_m_dtiles.ensure(nt * kTpKS * 64));
+    FRAC_HIP(c, c->d_m_dtiles.ensure(nt * kDftKS * 64));
     FRAC_HIP(c, c->d_m_dconst.ensure((size_t)nt * kDftCS * 4 + 256)); // Fourier layout + one DMA piece of slack
-    FRAC_HIP(c, c->d_m_rfrags.ensure(nbk * 7 * 64));
+    FRAC_HIP(c, c->d_m_rfrags.ensure(nbk * kDftNBF * 64));
     FRAC_HIP(c, c->d_m_rconst.ensure(nbk * 32));
     FRAC_HIP(c, c->d_dft_tguard.ensure(nt));
     FRAC_HIP(c, c->d_dft_trmax.ensure(nt + 4)); // + 4: a chunk's thresholds are one scalar load (tp_seed_windows)
@@ -816,13 +796,9 @@ int fill_mfma(frac_ctx* c)
     FRAC_HIP(c, c->d_m_dconst.ensure((size_t)c->ntiles * kDftCS * 4 + 256));
     FRAC_HIP(c, c->d_m_dtiles.ensure((size_t)c->ntiles * KS * 64));
     FRAC_HIP(c, c->d_m_rfrags.ensure((size_t)c->nblocks * std::max(c->Teff * KS, 6u * c->dft_copies) * 64));
-    FRAC_HIP(c, c->d_m_entries.ensure(std::max(c->m_work.size() * 4 * c->Teff, c->m8_work.size() * c->m8_bpw) *
-                                      64));
-    if (!c->m8_blk_ptr.empty()) { // built for n = 8, T = 4 (search_dft); may have no work
+    FRAC_HIP(c, c->d_m_entries.ensure(c->m_work.size() * 4 * c->Teff * 64)); // the direct form's (search_dft: none)
+    if (c->m8_built) // n = 8, T = 4 or 8 (search_dft); may have no work
         FRAC_TRY(upload(c, c->d_m8_work, c->m8_work));
-        FRAC_TRY(upload(c, c->d_m8_blk_ptr, c->m8_blk_ptr));
-        FRAC_TRY(upload(c, c->d_m8_blk_ent, c->m8_blk_ent));
-    }
     if (c->nblocks) {
         fill_range_slots<<<(c->nblocks * 32 + 255) / 256, 256, 0, c->stream>>>(
             c->mlayout, c->d_rord.ptr, c->nblocks * 32, c->d_m_slot_range.ptr, c->d_m_range_slot.ptr);

@@ -241,12 +241,12 @@ int qt_encode_dev(frac_ctx* c, const frac_quadtree_params* qp, LevelGrid& level,
         FRAC_HIP(c, c->d_m_dtiles.ensure((size_t)ntiles_cap * std::max(KS, 5u) * 64));
         FRAC_HIP(c, c->d_m_rfrags.ensure((size_t)nblocks_cap * std::max(T * KS, 6u * cp) * 64));
         DBuf<uint4>& dwork = fourier ? c->d_m8_work : c->d_m_work;
-        DBuf<uint32_t>& dptr = fourier ? c->d_m8_blk_ptr : c->d_m_blk_ptr;
-        DBuf<uint32_t>& dent = fourier ? c->d_m8_blk_ent : c->d_m_blk_ent;
         FRAC_HIP(c, dwork.ensure(nwork_cap));
-        FRAC_HIP(c, dptr.ensure((size_t)nblocks_cap * cp + 1));
-        FRAC_HIP(c, dent.ensure(nent_cap));
-        FRAC_HIP(c, c->d_m_entries.ensure((size_t)nwork_cap * (fourier ? kDftBlocksPerWG : 4u * T) * 64));
+        if (!fourier) { // the direct form's entries and their CSR map (the Fourier search merges per slot: none)
+            FRAC_HIP(c, c->d_m_blk_ptr.ensure((size_t)nblocks_cap * cp + 1));
+            FRAC_HIP(c, c->d_m_blk_ent.ensure(nent_cap));
+            FRAC_HIP(c, c->d_m_entries.ensure((size_t)nwork_cap * 4u * T * 64));
+        }
         FRAC_HIP(c, c->d_bk_cnt.ensure(((size_t)(nd + kBkTile - 1) / kBkTile + (nr_max + kBkTile - 1) / kBkTile + 2) *
                                        kMaxBuckets));
         tr.mark("level buffers");
@@ -290,8 +290,8 @@ int qt_encode_dev(frac_ctx* c, const frac_quadtree_params* qp, LevelGrid& level,
         pa.nblocks_cap = nblocks_cap;
         pa.ntiles_cap = ntiles_cap;
         pa.work = dwork.ptr;
-        pa.blk_ptr = dptr.ptr;
-        pa.blk_ent = dent.ptr;
+        pa.blk_ptr = fourier ? nullptr : c->d_m_blk_ptr.ptr;
+        pa.blk_ent = fourier ? nullptr : c->d_m_blk_ent.ptr;
         pa.acc = c->d_qt_stats.ptr;
         QtFillArgs& fa = pa.fill;
         fa.rord = c->d_rord.ptr;
@@ -305,7 +305,7 @@ int qt_encode_dev(frac_ctx* c, const frac_quadtree_params* qp, LevelGrid& level,
         fa.rconst = fourier ? nullptr : c->d_m_rconst.ptr;
         fa.best_key = c->d_best_key.ptr;
         fa.fb_count = c->d_fb_count.ptr;
-        // the layout, work lists, CSR map and per-item maps: one launch
+        // the layout, work lists, the direct form's CSR map and per-item maps: one launch
         qt_plan<<<std::max(32u, (fa.nthreads + 255) / 256), 256, 0, c->stream>>>(pa);
         // the level's search, on the bounds: launch_all in plan mode
         c->m_work.clear();
@@ -315,7 +315,6 @@ int qt_encode_dev(frac_ctx* c, const frac_quadtree_params* qp, LevelGrid& level,
         c->n_dev = n;
         c->ntiles = ntiles_cap;
         c->nblocks = nblocks_cap;
-        c->m8_bpw = kDftBlocksPerWG;
         c->qplan = plan;
         c->qp_nwork_cap = nwork_cap;
         const int rc = launch_all_n(c, n);

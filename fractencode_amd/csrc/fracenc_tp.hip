@@ -344,10 +344,10 @@ __global__ void __launch_bounds__(256) tp_prep(MfmaDomainPrepArgs d, DftDomainBu
     if (blockIdx.x < dblocks) {
         if (trmax && blockIdx.x == 0 && threadIdx.x < 4u)
             trmax[d.ntiles + threadIdx.x] = -1; // (padding: masked out by dft_guard_bits)
-        dft_domain_build_pair_at<kDftTpForm != 4, true>(blockIdx.x * blockDim.x + threadIdx.x, d, s, tguard, trmax,
+        dft_domain_build_pair_at<true>(blockIdx.x * blockDim.x + threadIdx.x, d, s, tguard, trmax,
                                                         stage);
     } else if (blockIdx.x < dblocks + rblocks) {
-        dft_range_prep_pair_at<kDftTpForm, true>((blockIdx.x - dblocks) * blockDim.x + threadIdx.x, r, rguard,
+        dft_range_prep_pair_at<true>((blockIdx.x - dblocks) * blockDim.x + threadIdx.x, r, rguard,
                                                          stage);
     } else {
         tp_seed_work_at((blockIdx.x - dblocks - rblocks) * blockDim.x + threadIdx.x, w.groups, w.ngroups, w.blk_sr,

@@ -157,12 +157,14 @@ def test_product_library_has_no_ablation_kernels():
     assert dft and mfma
     assert all(int(v) & (8 | 16 | 32 | 64 | 256 | 512) == 0 for v in dft), sorted(set(dft))
     assert all(int(v) & (8 | 16) == 0 for v in mfma), sorted(set(mfma))
-    # and no A/B variant either (round 4): the Fourier search as shipped (variant 35 =
-    # 1|kDftChain|kDft6|kDftFast6|kDftUnroll|kDftBufDma) and the SEA tiled form's exact six-MFMA
-    # tile (1|kDftChain|kDft6); the direct form's shipped schedule (130)
+    # and no A/B variant either (round 4): the Fourier search as shipped (variant 35, kDftFastVar)
+    # and the SEA tiled form's exact six-MFMA tile (kDftExactVar); the direct form's shipped schedule (130)
     assert set(map(int, dft)) == {123905, 9217}, sorted(set(dft))
     assert set(map(int, mfma)) == {130, 386}, sorted(set(mfma))  # 386: the float-C epilogue, n <= 4
-    assert not _kernel_instances(r"fracenc::(search_dft2)<"), "the two-block A/B form is tuning-only"
+    # the retired search and prep forms are in no build: one dft_prep, one fragment layout
+    assert len(_kernel_instances(r"(fracenc::dft_prep(?:<[^>]*>)?)\(")) == 1
+    for gone in ("dft_domain_build", "dft_range_prep", "search_dft2"):
+        assert not _kernel_instances(r"fracenc::(%s)[<(]" % gone), gone
 
 
 def test_uniform_grid_closed_form_count_and_cap(oracle):

@@ -415,7 +415,7 @@ def test_float_c_epilogue_at_operand_extremes(n, kind):
 @pytest.mark.parametrize("kind", ["binary", "blocks8", "orbits", "noise"])
 def test_t8_fourier_flipped_copies_at_operand_extremes(kind):
     """T = 8 on the Fourier path: each range block runs a second time read through Flip
-    (Flip_Rotate_k = Flip ∘ Rotate_k, dft_range_prep flip_from) and resolve_dft keeps the lesser key of
+    (Flip_Rotate_k = Flip ∘ Rotate_k, dft_range_prep_pair_at, flip_from) and resolve_dft keeps the lesser key of
     the two copies, with the copy's rotation t' as transform 4 + (−t' mod 4).  On the operand-extreme
     frames and on noise, with and without the classifier and with a hit threshold (the first hit in
     (domain, transform) order, image/metrics.h + TransformEstimator2.hpp:34-41), the records equal the

@@ -24,14 +24,14 @@ import lds_dma_check  # noqa: E402
 CSRC = os.path.join(ROOT, "fractencode_amd", "csrc")
 FAMILIES = ("search_dft<", "search_mfma<", "search_mfma16<")
 # one instance per family, as the product library instantiates them: the shipped C3 search first
-# (variant 35 = 1|kDftChain|kDft6|kDftFast6|kDftUnroll|kDftBufDma: buffer_load … lds stages and the
-# zero-tail reads of the guarded epilogue), then the SEA tiled form's exact six-MFMA tile (9217,
-# global_load_lds stages) and the direct form's shipped schedule for n <= 4 (386, the float-C epilogue)
+# (variant 35 = kDftFastVar, 123905: buffer_load … lds stages and the zero-tail reads of the guarded
+# epilogue), then the SEA tiled form's exact six-MFMA tile (kDftExactVar, 9217: global_load_lds stages;
+# template arguments HITS, VAR, CHUNKED — the workgroup is always 8 waves and the stage 4 tiles) and the direct form's shipped schedule for n <= 4 (386, the float-C epilogue)
 INSTANCES = {
-    "search_dft35": "template __global__ void fracenc::search_dft<false, 123905, 8u, 4u, false>(fracenc::DftArgs);",
-    "search_dft35_hits": "template __global__ void fracenc::search_dft<true, 123905, 8u, 4u, false>(fracenc::DftArgs);",
-    "search_dft": "template __global__ void fracenc::search_dft<false, 9217, 8u, 4u, true>(fracenc::DftArgs);",
-    "search_dft_hits": "template __global__ void fracenc::search_dft<true, 9217, 8u, 4u, true>(fracenc::DftArgs);",
+    "search_dft35": "template __global__ void fracenc::search_dft<false, 123905, false>(fracenc::DftArgs);",
+    "search_dft35_hits": "template __global__ void fracenc::search_dft<true, 123905, false>(fracenc::DftArgs);",
+    "search_dft": "template __global__ void fracenc::search_dft<false, 9217, true>(fracenc::DftArgs);",
+    "search_dft_hits": "template __global__ void fracenc::search_dft<true, 9217, true>(fracenc::DftArgs);",
     "search_mfma": "template __global__ void fracenc::search_mfma<4, 4, false, 386>(fracenc::MfmaSearchArgs);",
     "search_mfma16": "template __global__ void fracenc::search_mfma16<4, false>(fracenc::MfmaSearchArgs);",
 }

@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
 """Interleaved in-process A/B of MFMA search variants on the C3 frame; prints per-variant
 median/min search-kernel and finish (resolve + fit) ms (library HIP events).
-Variants: "d" = the C4-Fourier search (FRAC_MFMA_DFT=1, default: software-pipelined exact
-form), "e" = its unpipelined exact form, "g" = the guarded fast-path form, "d5" = the five-MFMA form (variant 20), "dt" = "d" with the pairwise-tree row maximum (the default uses one v_max3 chain), "p" = pipelined with a forced interleave, "em"/"ev" = MFMA-only / VALU-only ablations of "e", an integer v = the direct
-search_mfma with FRAC_MFMA_VARIANT=v (FRAC_MFMA_DFT=0).
+Variants: "d" = the C4-Fourier search as shipped (FRAC_MFMA_DFT=1; variant 35, also "fub"), "ft" = the same
+always carrying the winning chunk's tile mask (37), "d6" = its exact epilogue (21, the A/B of the guard),
+"fM" / "fV" / "fB" / "f0" = the ablations of 35 (240 – 243: MFMAs with a one-value epilogue, the epilogue
+without MFMAs, no barrier, no LDS-DMA / barrier; wrong results by design), an integer v = the direct
+search_mfma with FRAC_MFMA_VARIANT=v (FRAC_MFMA_DFT=0).  The search forms retired since (DESIGN §7.2,
+Appendix A) ran under letters this table no longer has.
 Ablation variants need the tuning library: python tools/build_tuning.py, then
 FRAC_LIB=fractencode_amd/libfracenc_tuning.so tools/ab_mfma.py ...
 usage: tools/ab_mfma.py d,2 [rounds]"""
@@ -31,15 +34,14 @@ with F.Engine(0, 4, False, 0.0, -1.0, F.ENGINE_MFMA, timing=True) as e:
     for r in range(rounds + 1):
         for v in variants:
             os.environ["FRAC_MFMA_DFT"] = "1" if not v.isdigit() else "0"
-            os.environ["FRAC_MFMA_VARIANT"] = {"d": "2", "e": "1", "g": "3", "p": "4", "d8": "5", "dt": "6", "d2": "12", "d5": "20", "d5s": "22", "d6": "21", "d62": "23", "d6f": "26", "d6w": "27", "d6fw": "28", "fu": "33", "fb": "34", "fub": "35", "fubp": "36", "d4": "24", "dm": "201", "dm0": "202", "dmD": "203", "dmB": "204", "dD": "205", "dB": "206",
-                                              "d0": "207", "dfB": "226", "df0": "227", "fM": "240", "fV": "241", "fB": "242", "f0": "243", "em": "9", "ev": "17", "emL": "41", "emB": "73",
-                                              "em0": "105", "eB": "65"}.get(v, v)
+            os.environ["FRAC_MFMA_VARIANT"] = {"d": "35", "fub": "35", "ft": "37", "d6": "21", "fM": "240", "fV": "241",
+                                              "fB": "242", "f0": "243"}.get(v, v)
             for _ in range(REPS):  # back-to-back runs: the last one is timed (the clock settles under load)
                 e.run()
             out, st = e.fetch()
             if ref is None:
                 ref = out.tobytes()
-            if v in ("d", "e", "g", "p", "d8", "dt", "d2", "d5", "d5s", "d6", "d62", "d6f", "d6w", "d6fw", "fu", "fb", "fub", "fubp", "d4") or (v.isdigit() and (int(v) < 8 or int(v) in (32, 64, 96, 98, 128, 130))):  # 8, 16 are ablations (results intentionally wrong)
+            if v in ("d", "fub", "ft", "d6") or (v.isdigit() and (int(v) < 8 or int(v) in (32, 64, 96, 98, 128, 130))):  # 8, 16 are ablations (results intentionally wrong)
                 assert out.tobytes() == ref, f"variant {v} differs"
             if r:
                 res[v].append(st["ms_search"])

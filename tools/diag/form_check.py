@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Diagnostic: records of a Fourier-form variant (FRAC_MFMA_VARIANT=argv[1]) against the VALU
-engine on a uniform-noise frame; prints the first mismatching ranges."""
+"""Diagnostic: records of a Fourier-form variant (FRAC_MFMA_VARIANT=argv[1]: 35 the shipped form, 37 with the
+tile mask, 21 the exact epilogue; the latter two in a tuning build) against the VALU engine on a uniform-noise
+frame; prints the first mismatching ranges."""
 import os
 import sys
 
@@ -9,7 +10,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import fractencode_amd as F  # noqa: E402
 
-var = sys.argv[1] if len(sys.argv) > 1 else "21"
+var = sys.argv[1] if len(sys.argv) > 1 else "35"
 S = int(sys.argv[2]) if len(sys.argv) > 2 else 128
 rng = np.random.default_rng(2000)
 p = rng.integers(0, 256, (S, S), dtype=np.uint8)
