@@ -273,6 +273,8 @@ def lib() -> C.CDLL:
             "frac_debug_bucket_self_tiles": (u32, []),
             "frac_debug_bucket_keys": (i32, [vp, vp, u32, vp, u32, i32, vp, vp]),
             "frac_debug_bucket_sort": (i32, [vp, u32, u32, vp, u32, u32, vp, vp, vp, vp]),
+            "frac_debug_frame_twin_bytes": (C.c_uint64, [vp]),
+            "frac_debug_frame_copy_stream": (i32, [vp]),
         }
         for name, (res, args) in sig.items():
             if os.environ.get("FRAC_LIB") and not hasattr(L, name):
@@ -323,6 +325,15 @@ def debug_sort_pairs(keys, vals, keys_b, vals_b, bits: int):
     if rc != 0:
         raise FracError(f"frac_debug_sort_pairs: {last_error()} (code {rc})")
     return tuple(outs)
+
+
+def debug_frame_upload(engine) -> dict:
+    """What the engine's context holds for overlapped frame uploads: twin_bytes, the capacity of its second
+    plane buffers (frac_debug_frame_twin_bytes), and copy_stream, whether its copy stream exists
+    (frac_debug_frame_copy_stream)."""
+    L = lib()
+    return {"twin_bytes": int(L.frac_debug_frame_twin_bytes(engine._ctx)),
+            "copy_stream": bool(L.frac_debug_frame_copy_stream(engine._ctx))}
 
 
 BK_TILE = 1024        # items per workgroup of the classifier bucket sort (frac_debug_bucket_tile)
@@ -557,7 +568,9 @@ class Engine:
         self._check(lib().frac_set_params(self._ctx, C.byref(self._p)))
 
     def set_frame(self, plane) -> None:
-        """Source == target plane (Encoder2).  numpy uint8 [H, W] or a CUDA torch tensor."""
+        """Source == target plane (Encoder2).  numpy uint8 [H, W] or a CUDA torch tensor.  A host plane has been
+        consumed when the call returns; after a frame of the same size its upload overlaps what is left of the
+        previous run() (frac_set_frame)."""
         self._frame_wh = (int(plane.shape[1]), int(plane.shape[0]))
         if hasattr(plane, "is_cuda") and plane.is_cuda:
             import torch

@@ -129,18 +129,97 @@ int classify_on_device(frac_ctx* c, const std::vector<frac_grid_item>& items, co
     return FRAC_OK;
 }
 
-// the caller's plane straight to the device (no host copy): pageable memory, so the copy is
-// complete, and the caller's buffer free again, when the call returns
-int upload_plane(frac_ctx* c, const uint8_t* p, uint32_t w, uint32_t h, uint32_t stride, DBuf<uint8_t>& d,
-                 uint32_t& dstride)
+// one host plane of an upload: the caller's memory, the buffer the runs read, its twin and its pitch
+struct PlaneUpload {
+    const uint8_t* p;
+    uint32_t w, h, stride;
+    DBuf<uint8_t>* cur;
+    DBuf<uint8_t>* next;
+    uint32_t* dstride;
+};
+
+// both of the context's streams idle: before a plane buffer or a twin is (re)allocated, nothing may still
+// read or write the one that goes
+int planes_idle(frac_ctx* c)
 {
-    dstride = plane_pitch(w);
-    // one extra row + column of slack: kernels never read it, but keeps every 2×2 read in-bounds
-    FRAC_HIP(c, d.ensure((size_t)dstride * (h + 1)));
-    if (h == 0 || w == 0)
-        return FRAC_OK;
-    FRAC_TRY(copy_plane(c, d.ptr, dstride, p, stride, w, h, hipMemcpyHostToDevice, c->stream));
     FRAC_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->frame.copy_stream)
+        FRAC_HIP(c, hipStreamSynchronize(c->frame.copy_stream));
+    return FRAC_OK;
+}
+
+// The caller's planes (the source, or source and target: `same`) straight to the device, for the blocking
+// setters (wait: the planes have been consumed, and may be overwritten, when the call returns) and for
+// frac_set_frame_async (no wait).  The first planes of a geometry go into the current buffers on the context's
+// stream, behind everything it holds.  Planes that follow others of their geometry go into the twins on the
+// copy stream (frac_ctx::FrameStream has the ordering) while the runs already enqueued go on: the host then
+// waits for the copies alone.  On an error the current planes, their pitches and the context's flags are as
+// they were: nothing swaps before every copy has been enqueued.
+int upload_planes(frac_ctx* c, const PlaneUpload* up, int n, bool same, bool wait)
+{
+    FRAC_TRY(settle_fallback(c)); // the last run's fp32-regime ranges read the current planes: before any swap
+    auto& f = c->frame;
+    uint32_t pitch[2] = {0, 0};
+    size_t need[2] = {0, 0};
+    for (int k = 0; k < n; ++k) {
+        pitch[k] = plane_pitch(up[k].w);
+        // one extra row + column of slack: kernels never read it, but keeps every 2×2 read in-bounds
+        need[k] = (size_t)pitch[k] * (up[k].h + 1);
+    }
+    bool twin = c->planes_set && c->same_plane == same && c->src.w == up[0].w && c->src.h == up[0].h;
+    if (twin && !same)
+        twin = c->tgt.w == up[1].w && c->tgt.h == up[1].h;
+    if (!twin) {
+        bool grow = false;
+        for (int k = 0; k < n; ++k)
+            grow = grow || !up[k].cur->ptr || up[k].cur->cap < need[k];
+        if (grow)
+            FRAC_TRY(planes_idle(c));
+        for (int k = 0; k < n; ++k)
+            FRAC_HIP(c, up[k].cur->ensure(need[k]));
+        for (int k = 0; k < n; ++k)
+            FRAC_TRY(copy_plane(c, up[k].cur->ptr, pitch[k], up[k].p, up[k].stride, up[k].w, up[k].h,
+                                hipMemcpyHostToDevice, c->stream));
+        if (wait)
+            FRAC_HIP(c, hipStreamSynchronize(c->stream));
+        for (int k = 0; k < n; ++k)
+            *up[k].dstride = pitch[k];
+        return FRAC_OK;
+    }
+    if (!f.copy_stream) {
+        FRAC_HIP(c, hipStreamCreateWithFlags(&f.copy_stream.s, hipStreamNonBlocking));
+        FRAC_HIP(c, hipEventCreateWithFlags(&f.up_done.e, hipEventDisableTiming));
+        FRAC_HIP(c, hipEventCreateWithFlags(&f.next_free.e, hipEventDisableTiming));
+    }
+    bool grow = false;
+    for (int k = 0; k < n; ++k)
+        grow = grow || !up[k].next->ptr || up[k].next->cap < need[k];
+    if (grow) { // an earlier upload may still write, an earlier run still read, the twin that goes
+        FRAC_TRY(planes_idle(c));
+        for (int k = 0; k < n; ++k)
+            FRAC_HIP(c, up[k].next->ensure(need[k]));
+    }
+    if (f.next_free_recorded) // the runs that read the twins before the last swap are done
+        FRAC_HIP(c, hipStreamWaitEvent(f.copy_stream, f.next_free, 0));
+    for (int k = 0; k < n; ++k) {
+        const int rc = copy_plane(c, up[k].next->ptr, pitch[k], up[k].p, up[k].stride, up[k].w, up[k].h,
+                                  hipMemcpyHostToDevice, f.copy_stream);
+        if (rc != FRAC_OK) { // no copy of this call may still read the caller's planes after it returned
+            (void)hipStreamSynchronize(f.copy_stream);
+            return rc;
+        }
+    }
+    FRAC_HIP(c, hipEventRecord(f.up_done, f.copy_stream));
+    FRAC_HIP(c, hipStreamWaitEvent(c->stream, f.up_done, 0));
+    for (int k = 0; k < n; ++k) {
+        std::swap(*up[k].cur, *up[k].next);
+        *up[k].dstride = pitch[k];
+    }
+    // the planes now in the twins are free once everything the context enqueued so far has run
+    FRAC_HIP(c, hipEventRecord(f.next_free, c->stream));
+    f.next_free_recorded = true;
+    if (wait)
+        FRAC_HIP(c, hipEventSynchronize(f.up_done));
     return FRAC_OK;
 }
 
@@ -175,6 +254,15 @@ const char* frac_last_error(const frac_ctx* ctx) { return ctx ? ctx->err.c_str()
 uint32_t frac_debug_sort_chunk(void) { return kTpSortChunk; }
 
 uint32_t frac_debug_resolve_group(void) { return kTpGrpItems; }
+
+// Test hook: what the context holds for overlapped uploads (frac_ctx::FrameStream): the twins' bytes, and
+// whether the copy stream exists.
+uint64_t frac_debug_frame_twin_bytes(const frac_ctx* c)
+{
+    return c ? (uint64_t)c->frame.d_src_next.cap + c->frame.d_tgt_next.cap : 0;
+}
+
+int frac_debug_frame_copy_stream(const frac_ctx* c) { return c && c->frame.copy_stream ? 1 : 0; }
 
 // Test hook: the tiled form's sort (tp_sort_pairs) on host arrays, both sides through the same launches on the
 // current device's null stream, then a synchronous copy back.
@@ -468,8 +556,10 @@ static void planes_changed(frac_ctx* c, uint32_t sw, uint32_t sh, uint32_t tw, u
     c->rate.ready = false;
 }
 
-int frac_set_planes(frac_ctx* c, const uint8_t* src, uint32_t sw, uint32_t sh, uint32_t sstride, const uint8_t* tgt,
-                    uint32_t tw, uint32_t th, uint32_t tstride)
+// the host-plane setters: the blocking ones wait until the planes have been consumed, frac_set_frame_async
+// does not (upload_planes)
+static int set_host_planes(frac_ctx* c, const uint8_t* src, uint32_t sw, uint32_t sh, uint32_t sstride,
+                           const uint8_t* tgt, uint32_t tw, uint32_t th, uint32_t tstride, bool wait)
 {
     if (!c)
         return FRAC_E_INVALID;
@@ -479,17 +569,22 @@ int frac_set_planes(frac_ctx* c, const uint8_t* src, uint32_t sw, uint32_t sh, u
     const bool same = tgt == nullptr || tgt == src;
     if (!same && (tw == 0 || th == 0 || tstride < tw))
         return c->fail(FRAC_E_INVALID, "invalid target plane");
-    FRAC_TRY(settle_fallback(c)); // the last run's fp32-regime ranges read the planes the uploads overwrite
-    FRAC_TRY(upload_plane(c, src, sw, sh, sstride, c->d_src, c->d_sstride));
-    if (!same)
-        FRAC_TRY(upload_plane(c, tgt, tw, th, tstride, c->d_tgt, c->d_tstride));
+    const PlaneUpload up[2] = {{src, sw, sh, sstride, &c->d_src, &c->frame.d_src_next, &c->d_sstride},
+                               {tgt, tw, th, tstride, &c->d_tgt, &c->frame.d_tgt_next, &c->d_tstride}};
+    FRAC_TRY(upload_planes(c, up, same ? 1 : 2, same, wait));
     planes_changed(c, sw, sh, same ? sw : tw, same ? sh : th, same);
     return FRAC_OK;
 }
 
+int frac_set_planes(frac_ctx* c, const uint8_t* src, uint32_t sw, uint32_t sh, uint32_t sstride, const uint8_t* tgt,
+                    uint32_t tw, uint32_t th, uint32_t tstride)
+{
+    return set_host_planes(c, src, sw, sh, sstride, tgt, tw, th, tstride, true);
+}
+
 int frac_set_frame(frac_ctx* c, const uint8_t* plane, uint32_t w, uint32_t h, uint32_t stride)
 {
-    return frac_set_planes(c, plane, w, h, stride, nullptr, 0, 0, 0);
+    return set_host_planes(c, plane, w, h, stride, nullptr, 0, 0, 0, true);
 }
 
 static int set_frame_device(frac_ctx* c, const void* d_plane, uint32_t w, uint32_t h, uint32_t stride, bool wait)
@@ -518,35 +613,7 @@ int frac_set_frame_device(frac_ctx* c, const void* d_plane, uint32_t w, uint32_t
 // Frame streaming from host memory (frac_ctx::FrameStream has the ordering)
 int frac_set_frame_async(frac_ctx* c, const uint8_t* plane, uint32_t w, uint32_t h, uint32_t stride)
 {
-    if (!c)
-        return FRAC_E_INVALID;
-    if (!plane || w == 0 || h == 0 || stride < w)
-        return c->fail(FRAC_E_INVALID, "invalid plane");
-    FRAC_HIP(c, hipSetDevice(c->device));
-    FRAC_TRY(settle_fallback(c)); // the last run's fp32-regime ranges read the current plane
-    auto& f = c->frame;
-    if (!f.copy_stream) {
-        FRAC_HIP(c, hipStreamCreateWithFlags(&f.copy_stream.s, hipStreamNonBlocking));
-        FRAC_HIP(c, hipEventCreateWithFlags(&f.up_done.e, hipEventDisableTiming));
-        FRAC_HIP(c, hipEventCreateWithFlags(&f.next_free.e, hipEventDisableTiming));
-    }
-    const uint32_t dstride = plane_pitch(w);
-    if (f.d_src_next.cap < (size_t)dstride * (h + 1)) { // a (re)allocation: nothing may still read the buffer
-        FRAC_HIP(c, hipStreamSynchronize(c->stream));
-        FRAC_HIP(c, f.d_src_next.ensure((size_t)dstride * (h + 1)));
-    }
-    if (f.next_free_recorded) // the runs that read this buffer before the last swap are done
-        FRAC_HIP(c, hipStreamWaitEvent(f.copy_stream, f.next_free, 0));
-    FRAC_TRY(copy_plane(c, f.d_src_next.ptr, dstride, plane, stride, w, h, hipMemcpyHostToDevice, f.copy_stream));
-    FRAC_HIP(c, hipEventRecord(f.up_done, f.copy_stream));
-    FRAC_HIP(c, hipStreamWaitEvent(c->stream, f.up_done, 0));
-    std::swap(c->d_src, f.d_src_next);
-    c->d_sstride = dstride;
-    // the plane now in d_src_next is free once everything the context enqueued so far has run
-    FRAC_HIP(c, hipEventRecord(f.next_free, c->stream));
-    f.next_free_recorded = true;
-    planes_changed(c, w, h, w, h, true);
-    return FRAC_OK;
+    return set_host_planes(c, plane, w, h, stride, nullptr, 0, 0, 0, false);
 }
 
 int frac_set_frame_device_async(frac_ctx* c, const void* d_plane, uint32_t w, uint32_t h, uint32_t stride)

@@ -119,14 +119,16 @@ struct frac_ctx {
     // the streams come before every buffer: members go in reverse order, the buffers first
     Stream own_stream;
     hipStream_t stream = nullptr; // own_stream, or the caller's (frac_set_stream)
-    // frac_set_frame_async (ABI 9): the frame after the current one is uploaded into d_src_next on copy_stream
-    // while the context's stream still reads d_src; the two swap at the call (created on first use).
-    // Frame streaming from host memory: the upload runs on the context's copy stream into the plane buffer the
-    // current runs do not read, after the runs that last read that buffer (next_free); the context's stream waits
-    // for the upload (up_done) and the buffers swap, so frame k+1 crosses PCIe while frame k searches.
+    // Host planes after the first of a geometry (frac_set_frame, frac_set_planes, frac_set_frame_async: one
+    // helper, upload_planes in fracenc_api.hip): the upload runs on the context's copy stream into the twin of
+    // each plane buffer, which the runs already enqueued do not read, after the runs that last read that twin
+    // (next_free); the context's stream waits for the upload (up_done) and the buffers swap, so frame k+1 crosses
+    // PCIe while frame k's kernels still run.  The blocking setters then wait for up_done alone, not for the
+    // context's stream.  Everything here is created on the first frame that has a predecessor of its geometry:
+    // a one-shot encode has no twin and no copy stream.
     struct FrameStream {
         Stream copy_stream;
-        DBuf<uint8_t> d_src_next;
+        DBuf<uint8_t> d_src_next, d_tgt_next;
         Event up_done, next_free;
         bool next_free_recorded = false;
     } frame;

@@ -178,7 +178,14 @@ int frac_set_params(frac_ctx* ctx, const frac_params* params);
  * frac_set_frame: source == target (what Encoder2 does, encode/Encoder2.hpp:36).
  * frac_set_planes: distinct source (domain) and target (range) planes, as
  * TransformEstimator2's constructor allows (encode/TransformEstimator2.hpp:15-21).
- * Every plane setter below ends the last run's results until the next frac_run. */
+ * Every plane setter below ends the last run's results until the next frac_run.
+ * Both calls block: on return the caller's planes have been consumed and may be overwritten or freed.  They do
+ * not wait for the runs already enqueued.  The first planes of a geometry go into the context's plane buffers on
+ * its stream.  Planes that follow others of the same geometry (sizes, and whether a distinct target is given)
+ * are uploaded on a copy stream of the context's own into a second buffer per plane, while the kernels of the
+ * previous frac_run still run; the context's stream waits for the upload and the buffers swap, so in a loop of
+ * frac_set_frame; frac_run the upload of frame k+1 overlaps what is left of frame k's run.  A context that is
+ * given one frame only allocates no second buffer and creates no stream. */
 int frac_set_frame(frac_ctx* ctx, const uint8_t* plane, uint32_t w, uint32_t h, uint32_t stride);
 int frac_set_planes(frac_ctx* ctx, const uint8_t* src, uint32_t sw, uint32_t sh, uint32_t sstride,
                     const uint8_t* tgt, uint32_t tw, uint32_t th, uint32_t tstride);
@@ -190,10 +197,11 @@ int frac_set_frame_device(frac_ctx* ctx, const void* d_plane, uint32_t w, uint32
  * context's stream has passed the copy (an event recorded on it after this call).  The first frame of a
  * geometry, or any frame with the classifier on, re-prepares on the host in the next frac_run. */
 int frac_set_frame_device_async(frac_ctx* ctx, const void* d_plane, uint32_t w, uint32_t h, uint32_t stride);
-/* ABI 9: frame streaming from host memory.  The plane (pinned host memory for an asynchronous copy) is uploaded
- * on the context's own copy stream into a second plane buffer while the runs already enqueued still read the
- * current one; the context's stream waits for the upload and the buffers swap.  frac_run right after it
- * searches the new frame, so frame k+1 crosses PCIe while frame k searches.  The host plane must stay unchanged
+/* ABI 9: frame streaming from host memory: frac_set_frame without the host's wait for the upload.  The plane
+ * (pinned host memory for an asynchronous copy) is uploaded as frac_set_frame uploads it: after a frame of the
+ * same geometry on the context's own copy stream into the second plane buffer while the runs already enqueued
+ * still read the current one; the context's stream waits for the upload and the buffers swap.  frac_run right
+ * after it searches the new frame, so frame k+1 crosses PCIe while frame k searches.  The host plane must stay unchanged
  * until the upload is done: until a later frac_sync / frac_fetch, or an event recorded on the context's stream
  * after this call. */
 int frac_set_frame_async(frac_ctx* ctx, const uint8_t* plane, uint32_t w, uint32_t h, uint32_t stride);
@@ -661,6 +669,11 @@ int frac_debug_sort_pairs(const uint32_t* keys, const uint32_t* vals, uint32_t n
  * sort that runs without the separate scan launch. */
 uint32_t frac_debug_bucket_tile(void);
 uint32_t frac_debug_bucket_self_tiles(void);
+/* frac_debug_frame_twin_bytes is the capacity of the second plane buffers the overlapped uploads of
+ * frac_set_frame / frac_set_planes / frac_set_frame_async use (0: none allocated); frac_debug_frame_copy_stream
+ * is 1 once the context has created its copy stream. */
+uint64_t frac_debug_frame_twin_bytes(const frac_ctx* ctx);
+int frac_debug_frame_copy_stream(const frac_ctx* ctx);
 int frac_debug_bucket_keys(frac_ctx* ctx, const frac_grid_item* doms, uint32_t nd, const frac_grid_item* rngs,
                            uint32_t nr, int path, uint32_t* dom_keys, uint32_t* rng_keys);
 int frac_debug_bucket_sort(const uint32_t* keys_a, uint32_t na, uint32_t dn_a, const uint32_t* keys_b, uint32_t nb,
