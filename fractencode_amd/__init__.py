@@ -15,6 +15,7 @@ The names mirror the reference's engine API for this path
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -251,6 +252,12 @@ def lib() -> C.CDLL:
                                            C.POINTER(u32), C.POINTER(C.c_uint64)]),
             "frac_quadtree_rd_leaves": (i32, [vp, u32, u32, C.c_uint64, vp, sz, C.POINTER(sz)]),
             "frac_quadtree_rd_stream": (i32, [vp, C.c_uint64, u32, u32, vp, sz, C.POINTER(sz)]),
+            "frac_decode_error": (i32, [vp, vp, sz, i32, C.c_double, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp,
+                                        sz, C.POINTER(sz), C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+            "frac_quadtree_rate_errors": (i32, [vp, u32, u32, vp, sz, i32, C.c_double, vp, vp, vp]),
+            "frac_quadtree_rate_quality": (i32, [vp, u32, u32, C.c_uint64, i32, C.c_double, C.POINTER(C.c_double),
+                                                 C.POINTER(C.c_uint64), C.POINTER(u32), C.POINTER(C.c_uint64),
+                                                 C.POINTER(u32)]),
             "frac_rgb_to_yuv_device": (i32, [vp, vp, u32, u32, u32, vp, u32, vp, u32, vp, u32]),
             "frac_rgb_to_yuv": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]),
             "frac_yuv_to_rgb_device": (i32, [vp, vp, u32, u32, u32, vp, u32, vp, u32, vp, u32]),
@@ -504,6 +511,11 @@ def hit_limit(rms_threshold: float, n: int) -> int:
 
 
 # ---- engine ---------------------------------------------------------------------
+
+def _psnr(sse: int, pixels: int) -> float:
+    """10·log10(255²·pixels / sse); inf at sse == 0."""
+    return math.inf if sse == 0 else 10.0 * math.log10(255.0 ** 2 * pixels / sse)
+
 
 class Engine:
     """One search context on one GPU (an AbstractEncodingEngine2 that takes batches).
@@ -972,6 +984,82 @@ class Engine:
         else:
             stream = self.rate_stream(t, contrast_bits, brightness_bits)
         info.update(split_distance=t, bytes=size, items=n)
+        return stream, info
+
+    def decode_error(self, stream, max_iter: int = -1, rms_eps: float = 1e-5, blocks: bool = False) -> dict:
+        """The decoded error of an FRC1 or FRQ1 stream against the frame set on this engine (frac_decode_error):
+        decoded at scale 1 on the device and compared there with the plane the ranges lie on, over the rectangle the
+        g × g grid covers (g: the FRC1 range size or the FRQ1 max_size); no plane crosses PCIe.  Returns a dict
+        with sse, pixels, psnr (10·log10(255²·pixels / sse), inf at sse == 0), iterations and rms; with `blocks`
+        also block_sse, the uint64 [H // g, W // g] sums of the g × g blocks."""
+        buf = np.frombuffer(stream, dtype=np.uint8)
+        sse, pixels, nb = C.c_uint64(0), C.c_uint64(0), C.c_size_t(0)
+        it, rms = C.c_int(0), C.c_double(0.0)
+        bmap = None
+        if blocks:
+            h = frq1_info(stream) if bytes(buf[:4]) == b"FRQ1" else frc1_info(stream)
+            g = h["max_size"] if "max_size" in h else h["range_size"]
+            bmap = np.zeros((h["height"] // g, h["width"] // g) if g else (0, 0), np.uint64)
+        self._check(lib().frac_decode_error(self._ctx, buf.ctypes.data, len(buf), max_iter, rms_eps, C.byref(sse),
+                                            C.byref(pixels), bmap.ctypes.data if blocks and bmap.size else None,
+                                            bmap.size if blocks else 0, C.byref(nb), C.byref(it), C.byref(rms)))
+        out = {"sse": sse.value, "pixels": pixels.value, "psnr": _psnr(sse.value, pixels.value),
+               "iterations": it.value, "rms": rms.value}
+        if blocks:
+            if nb.value != bmap.size:
+                raise FracError(f"decode_error: {nb.value} blocks, {bmap.size} expected")
+            out["block_sse"] = bmap
+        return out
+
+    def rate_errors(self, splits, contrast_bits: int = 5, brightness_bits: int = 7, max_iter: int = -1,
+                    rms_eps: float = 1e-5):
+        """Per split distance in `splits` the decoded error of the rate state's stream there
+        (frac_quadtree_rate_errors): decode_error(rate_stream(t)) without a plane or a leaf crossing PCIe.
+        Returns (sse uint64 [n], bytes uint64 [n], iterations int32 [n])."""
+        t = np.ascontiguousarray(splits, dtype=np.float64).reshape(-1)
+        n = len(t)
+        sse, size, it = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(n, np.int32)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if n else None  # noqa: E731
+        self._check(lib().frac_quadtree_rate_errors(self._ctx, contrast_bits, brightness_bits, ptr(t), n, max_iter,
+                                                    rms_eps, ptr(sse), ptr(size), ptr(it)))
+        return sse, size, it
+
+    def _rate_pixels(self) -> int:
+        """The area the rate state's level-0 grid covers (0 before a build)."""
+        W, H = self._frame_wh
+        g = getattr(self, "_rate_sizes", (0, 0))[0]
+        return (W - W % g) * (H - H % g) if g else 0
+
+    def rate_quality(self, max_sse: int | None = None, min_psnr: float | None = None, contrast_bits: int = 5,
+                     brightness_bits: int = 7, max_iter: int = -1, rms_eps: float = 1e-5):
+        """A split distance of the rate state whose decoded error is within the target, by the bisection
+        include/fracenc.h states for frac_quadtree_rate_quality → (split distance, bytes, leaves, sse, probes).
+        Exactly one of max_sse and min_psnr is given; min_psnr becomes max_sse = floor(255²·pixels / 10^(psnr/10)).
+        The answer meets the target and the next larger candidate does not (unless it is the largest); the decoded
+        error is not monotone in the split distance, so it need not be the largest candidate that meets it —
+        rate_errors over the candidates answers that.  FracError when the smallest split distance fails."""
+        if (max_sse is None) == (min_psnr is None):
+            raise ValueError("rate_quality: exactly one of max_sse and min_psnr")
+        if max_sse is None:
+            max_sse = int(math.floor(255.0 ** 2 * self._rate_pixels() / 10.0 ** (min_psnr / 10.0)))
+        t, size, leaves, sse, probes = C.c_double(0.0), C.c_uint64(0), C.c_uint32(0), C.c_uint64(0), C.c_uint32(0)
+        self._check(lib().frac_quadtree_rate_quality(self._ctx, contrast_bits, brightness_bits, int(max_sse), max_iter,
+                                                     rms_eps, C.byref(t), C.byref(size), C.byref(leaves),
+                                                     C.byref(sse), C.byref(probes)))
+        return t.value, size.value, leaves.value, sse.value, probes.value
+
+    def encode_quadtree_to_psnr(self, min_psnr: float, max_size: int = 16, min_size: int = 4,
+                                contrast_bits: int = 5, brightness_bits: int = 7, max_iter: int = -1,
+                                rms_eps: float = 1e-5):
+        """A quadtree partition of the frame set on this engine whose decoded PSNR is at least min_psnr:
+        quadtree_rate + rate_quality + rate_stream.  Returns (bytes, info): info has the stats of the full-tree
+        search plus split_distance, bytes, items, sse, pixels, psnr and probes."""
+        info = self.quadtree_rate(max_size, min_size)
+        t, size, n, sse, probes = self.rate_quality(None, min_psnr, contrast_bits, brightness_bits, max_iter, rms_eps)
+        stream = self.rate_stream(t, contrast_bits, brightness_bits)
+        pixels = self._rate_pixels()
+        info.update(split_distance=t, bytes=size, items=n, sse=sse, pixels=pixels, psnr=_psnr(sse, pixels),
+                    probes=probes)
         return stream, info
 
     def classify(self, items: np.ndarray, target_plane: bool = False) -> np.ndarray:

@@ -8,6 +8,7 @@
 //   fracenc_codec.hip    decode, FRC1 and FRQ1 pack / parse / decode, colour conversion
 //   fracenc_qtrate.hip   quadtree rate sweep: the full tree searched once, sizes, fit and leaves per threshold
 //   fracenc_qtrd.hip     rate–distortion-optimal partitions of that tree: sizes, fit, leaves and stream per multiplier
+//   fracenc_quality.hip  decoded error of a stream against the frame; the rate state's errors and quality fit
 //
 // Host logic mirrored from the reference:
 //   classifier gating      encode/Classifier2.cpp:8-81   (categories computed on the host,
@@ -51,6 +52,7 @@ using namespace fracenc;
 #include "fracenc_qtrate.hip"
 #include "fracenc_frq1pack.hip"
 #include "fracenc_qtrd.hip"
+#include "fracenc_quality.hip"
 
 namespace {
 

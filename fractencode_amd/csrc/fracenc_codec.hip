@@ -169,14 +169,20 @@ static bool covers_exactly(const std::vector<frac_grid_item>& rects, uint32_t w,
 // over a stream's records); decode_check, the buffer swap and the host's look at the flag every few steps
 // are shared.
 // Where a decode's plane comes from and goes to.  The initial target is a host plane (stride w) or, absent,
-// zeros; the decoded plane goes to a host plane (stride w; the call returns synchronised) or stays on the
-// device, copied to d_out with its pitch on the context's stream.
+// zeros; the decoded plane goes to a host plane (stride w; the call returns synchronised), or stays on the
+// device, copied to d_out with its pitch on the context's stream, or goes nowhere: `final` then learns which
+// decoder buffer holds it, and its pitch, once the context's stream has run (fracenc_quality.hip compares it
+// with the frame there).
 struct PlaneIO {
     const uint8_t* h_init = nullptr;
     uint8_t* h_out = nullptr;
     uint8_t* d_out = nullptr;
     uint32_t d_pitch = 0;
-    bool valid() const { return h_out || d_out; }
+    struct Final {
+        const uint8_t* ptr = nullptr;
+        uint32_t pitch = 0;
+    }* final = nullptr;
+    bool valid() const { return h_out || d_out || final; }
 };
 // the public decoders' plane: host in, host out
 static PlaneIO host_plane(uint8_t* plane)
@@ -189,7 +195,10 @@ static PlaneIO host_plane(uint8_t* plane)
 // the decoded plane `fin` (on the device, row pitch `stride`) to its destination
 static int decode_deliver(frac_ctx* c, const PlaneIO& io, const uint8_t* fin, uint32_t stride, uint32_t w, uint32_t h)
 {
-    if (io.h_out) {
+    if (io.final) {
+        io.final->ptr = fin;
+        io.final->pitch = stride;
+    } else if (io.h_out) {
         FRAC_HIP(c, hipMemcpy2DAsync(io.h_out, w, fin, stride, w, h, hipMemcpyDeviceToHost, c->stream));
         FRAC_HIP(c, hipStreamSynchronize(c->stream));
     } else {

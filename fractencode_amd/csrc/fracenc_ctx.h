@@ -74,6 +74,35 @@ struct Pinned {
     T* operator->() const { return ptr; }
 };
 
+// pinned host bytes that only grow
+struct PinnedBytes {
+    uint8_t* ptr = nullptr;
+    size_t cap = 0;
+    PinnedBytes() = default;
+    PinnedBytes(PinnedBytes&& o) noexcept : ptr(o.ptr), cap(o.cap) { o.ptr = nullptr, o.cap = 0; }
+    ~PinnedBytes() { release(); }
+    hipError_t ensure(size_t n)
+    {
+        if (n <= cap && ptr)
+            return hipSuccess;
+        release();
+        const size_t want = std::max<size_t>(n, 1);
+        hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&ptr), want);
+        if (e == hipSuccess)
+            cap = want;
+        return e;
+    }
+
+private:
+    void release()
+    {
+        if (ptr)
+            (void)hipHostFree(ptr);
+        ptr = nullptr;
+        cap = 0;
+    }
+};
+
 // an event, created by its user (the flags differ) into `e`
 struct Event {
     hipEvent_t e = nullptr;
@@ -356,6 +385,15 @@ struct frac_ctx {
         DBuf<Fit> d_fit;                  // frac_quadtree_rd_fit: the interval between the rounds
         Pinned<Fit> h_fit;                // mapped: its answer
     } rd;
+    // decoded error (fracenc_quality.hip): the covered rectangle's sum and its block sums, the sum's pinned
+    // landing place, the rate readers' stream on its way from the packer to the decoder, and the rate state's
+    // sorted keys on the host (the quality fit's candidates)
+    struct Quality {
+        DBuf<unsigned long long> d_total, d_block;
+        Pinned<unsigned long long> h_total;
+        PinnedBytes stream;
+        std::vector<unsigned long long> skey;
+    } quality;
     DBuf<uint8_t> d_sea_tmp;
     DBuf<unsigned long long> d_sea_count; // candidates the SEA search evaluated
     DBuf<unsigned long long> d_tp_evals;  // tiled form: per group, the (range, domain) pairs of its window

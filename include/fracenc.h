@@ -574,6 +574,55 @@ int frac_quadtree_rd_leaves(frac_ctx* ctx, uint32_t contrast_bits, uint32_t brig
 int frac_quadtree_rd_stream(frac_ctx* ctx, uint64_t lambda, uint32_t contrast_bits, uint32_t brightness_bits,
                             uint8_t* out, size_t cap, size_t* n_out);
 
+/* ---- decoded quality: the error of a stream against the frame, and the rate state steered by it ----
+ * These three symbols were added after ABI 9 without changing FRAC_ABI_VERSION: probe for them by name
+ * (dlsym) when the library may be older.
+ *
+ * The search's distances are collage errors.  These calls measure what a viewer gets: the stream decoded (after
+ * quantization, iterated to convergence) against the frame set on ctx — the plane the ranges lie on, the target
+ * plane when frac_set_planes gave one.  The decoded plane, the frame and the leaves stay on the device; only
+ * scalars (and, when asked, the block sums) come back.  Every sum is an exact unsigned 64-bit integer.
+ *
+ * frac_decode_error: `stream` is an FRC1 or an FRQ1 stream, told apart by its magic, parsed and validated as
+ * frac_decode_frc1 / frac_decode_frq1 do and decoded at scale 1 from a zero plane with max_iter and rms_eps as
+ * there.  Its width and height must be the frame's (FRAC_E_INVALID); no frame set is FRAC_E_STATE.  With g the
+ * FRC1 range_size or the FRQ1 max_size, the covered rectangle is (W − W % g) × (H − H % g) from the origin —
+ * what a uniform range grid or the level-0 grid covers: *pixels is its area, *sse is Σ(decoded − frame)² over
+ * it, and block_sse (may be NULL) gets the sums of its g × g blocks, row-major, (W / g)·(H / g) of them:
+ * min(count, block_cap) entries are written and *n_blocks is the count.  A leaf or record without a domain leaves
+ * its pixels at zero and is counted like any other.  A frame smaller than g gives pixels = sse = 0.  Every
+ * output pointer may be NULL.  The frame compared is the one the next frac_run would search: the call is
+ * ordered behind a pending frac_set_frame_async copy.  It returns synchronised.  It is a reader: a run's readable
+ * results, the rate state and the tuple sink are left alone; only the decoder's buffers are touched.
+ *
+ * frac_quadtree_rate_errors and frac_quadtree_rate_quality are rate readers, with frac_quadtree_rate_sizes' state
+ * rules (FRAC_E_STATE without a readable rate state; widths outside [2, 16] are FRAC_E_INVALID before any launch;
+ * they search nothing and leave the state and a run's readable results alone).
+ *  - _errors: for each of n split distances the stream frac_quadtree_rate_stream packs there, decoded and
+ *    compared as above: sse[n], bytes[n] (the stream's size) and iterations[n], each of which may be NULL.  Every
+ *    probe equals frac_decode_error of frac_quadtree_rate_stream's bytes.
+ *  - _quality: a split distance whose decoded error is at most max_sse.  With c[0] < … < c[m − 1] the state's
+ *    candidates {0.0} ∪ {e(v)}, E(i) the decoded sse at c[i] and meets(i) = E(i) ≤ max_sse, the rule is exactly:
+ *      1. probe m − 1; if it meets, the answer is m − 1;
+ *      2. otherwise, when m > 1, probe 0; if it fails (or m = 1), FRAC_E_INVALID, the message naming E(0);
+ *      3. lo = 0, hi = m − 1; while hi − lo > 1: mid = lo + (hi − lo) / 2; probe mid; lo = mid if it meets,
+ *         else hi = mid;
+ *      4. the answer is lo.
+ *    Outputs (each may be NULL): c[answer], its stream's bytes and leaves, E(answer) and the probes made.
+ *    Guarantee: the answer meets the target and the next larger candidate does not, unless the answer is the
+ *    largest candidate.  The decoded error is NOT monotone in the split distance, so the answer need not be the
+ *    largest candidate that meets the target; a caller who needs that sweeps the candidates with _errors.
+ *    An empty state (no level-0 ranges) has m = 1, E = 0: 64 bytes, no leaves, one probe. */
+int frac_decode_error(frac_ctx* ctx, const uint8_t* stream, size_t len, int max_iter, double rms_eps, uint64_t* sse,
+                      uint64_t* pixels, uint64_t* block_sse, size_t block_cap, size_t* n_blocks, int* iterations,
+                      double* rms);
+int frac_quadtree_rate_errors(frac_ctx* ctx, uint32_t contrast_bits, uint32_t brightness_bits, const double* split,
+                              size_t n, int max_iter, double rms_eps, uint64_t* sse, uint64_t* bytes,
+                              int* iterations);
+int frac_quadtree_rate_quality(frac_ctx* ctx, uint32_t contrast_bits, uint32_t brightness_bits, uint64_t max_sse,
+                               int max_iter, double rms_eps, double* split, uint64_t* bytes, uint32_t* leaves,
+                               uint64_t* sse, uint32_t* probes);
+
 /* ---- FRC3: one colour frame — the Y, U and V plane streams in one container, decoded to RGB on the device ----
  * These four symbols were added after ABI 9 without changing FRAC_ABI_VERSION: probe for them by name
  * (dlsym) when the library may be older.

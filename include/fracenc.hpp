@@ -13,8 +13,8 @@
 //   Quantizer<T>        Frac::Quantizer (encode/Quantizer.hpp:7-45) as the built reference
 //                       computes it (value() with the FMA the compiler contracts)
 //   createUniformGrid / preclassify / encodeQuadtree / decode / decode_frc1 / frc1_info / decode_frq1 / frq1_info /
-//                       pack_frq1 / decode_frc3 / frc3_info / quadtreeRate, rateSizes, rateFit, rateLeaves —
-//                       the C ABI entry points
+//                       pack_frq1 / decode_frc3 / frc3_info / quadtreeRate, rateSizes, rateFit, rateLeaves /
+//                       decodeError, rateErrors, rateQuality — the C ABI entry points
 //   Engine's ABI 8/9 methods: an external HIP stream (void*), the tuple sink and 32-byte tuples,
 //                       frame streaming (setFrameAsync / setFrameDeviceAsync), 32-byte quadtree
 //                       leaves, per-run device times
@@ -30,6 +30,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <stdexcept>
 #include <string>
@@ -277,6 +278,75 @@ public:
         check(frac_quadtree_rate_leaves(ctx_, split_distance, out.data(), cap, &n));
         out.resize(n < cap ? n : cap);
         return out;
+    }
+    // Decoded quality (probe for the symbols by name when the library may be older; include/fracenc.h states
+    // the rules).  decodeError: an FRC1 or FRQ1 stream decoded on the device and compared there with the frame
+    // set on this engine, over the rectangle its g × g grid covers; block_sse, when given, receives the
+    // (W / g)·(H / g) block sums, row-major.
+    struct DecodeError {
+        uint64_t sse, pixels;
+        int iterations;
+        double rms;
+        // 10·log10(255²·pixels / sse); +inf at sse == 0
+        double psnr() const
+        {
+            return sse ? 10.0 * std::log10(255.0 * 255.0 * (double)pixels / (double)sse)
+                       : std::numeric_limits<double>::infinity();
+        }
+    };
+    DecodeError decodeError(const uint8_t* stream, size_t len, int max_iter = -1, double rms_eps = 1e-5,
+                            std::vector<uint64_t>* block_sse = nullptr)
+    {
+        DecodeError r{};
+        size_t n = 0;
+        if (block_sse) { // sized from the header; a stream the parsers refuse throws there
+            uint32_t W, H, g;
+            if (stream && len >= 4 && std::memcmp(stream, "FRQ1", 4) == 0) {
+                const Frq1Info i = frq1_info(stream, len);
+                W = i.width, H = i.height, g = i.max_size;
+            } else {
+                const Frc1Info i = frc1_info(stream, len);
+                W = i.width, H = i.height, g = i.range_size;
+            }
+            n = g ? (size_t)(W / g) * (H / g) : 0;
+            block_sse->assign(n, 0);
+        }
+        check(frac_decode_error(ctx_, stream, len, max_iter, rms_eps, &r.sse, &r.pixels,
+                                block_sse && n ? block_sse->data() : nullptr, n, &n, &r.iterations, &r.rms));
+        return r;
+    }
+    // per split distance of the rate state the decoded sse; the streams' bytes and the iterations when asked for
+    std::vector<uint64_t> rateErrors(const std::vector<double>& split, uint32_t contrast_bits = 5,
+                                     uint32_t brightness_bits = 7, int max_iter = -1, double rms_eps = 1e-5,
+                                     std::vector<uint64_t>* bytes = nullptr, std::vector<int>* iterations = nullptr)
+    {
+        std::vector<uint64_t> sse(split.size());
+        if (bytes)
+            bytes->resize(split.size());
+        if (iterations)
+            iterations->resize(split.size());
+        check(frac_quadtree_rate_errors(ctx_, contrast_bits, brightness_bits, split.data(), split.size(), max_iter,
+                                        rms_eps, sse.data(), bytes ? bytes->data() : nullptr,
+                                        iterations ? iterations->data() : nullptr));
+        return sse;
+    }
+    struct RateQuality {
+        double split_distance;
+        uint64_t bytes;
+        uint32_t leaves;
+        uint64_t sse;
+        uint32_t probes;
+    };
+    // a split distance whose decoded sse is at most max_sse while the next larger candidate's is not (the stated
+    // bisection; not necessarily the largest that meets it: the error is not monotone); throws when the smallest
+    // split distance fails
+    RateQuality rateQuality(uint64_t max_sse, uint32_t contrast_bits = 5, uint32_t brightness_bits = 7,
+                            int max_iter = -1, double rms_eps = 1e-5)
+    {
+        RateQuality q{};
+        check(frac_quadtree_rate_quality(ctx_, contrast_bits, brightness_bits, max_sse, max_iter, rms_eps,
+                                         &q.split_distance, &q.bytes, &q.leaves, &q.sse, &q.probes));
+        return q;
     }
     // Decoder2::decode (encode/Encoder2.hpp:67-88); plane holds the caller's initial target
     // (main.cpp zeroes it) and receives the result.  Returns {iterations, rms}.
