@@ -268,6 +268,12 @@ def lib() -> C.CDLL:
                                        C.POINTER(C.c_double)]),
             "frac_decode_frc3_device": (i32, [vp, vp, sz, u32, i32, C.c_double, vp, u32, sz, C.POINTER(C.c_int),
                                               C.POINTER(C.c_double)]),
+            "frac_decode_error_frc3": (i32, [vp, vp, sz, vp, u32, i32, C.c_double, C.POINTER(C.c_uint64),
+                                             C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+            "frac_decode_error_frc3_device": (i32, [vp, vp, sz, vp, u32, i32, C.c_double, C.POINTER(C.c_uint64),
+                                                    C.POINTER(C.c_uint64), C.POINTER(C.c_int),
+                                                    C.POINTER(C.c_double)]),
+            "frac_quadtree_rate_candidates": (i32, [vp, vp, sz, C.POINTER(sz)]),
             "frac_uniform_grid": (sz, [u32, u32, u32, u32, vp, sz]),
             "frac_uniform_grid2": (sz, [u32, u32, u32, u32, u32, u32, vp, sz]),
             "frac_classify": (i32, [vp, u32, u32, u32, vp, sz]),
@@ -1164,6 +1170,58 @@ class Engine:
                                            rgb.ctypes.data, 3 * W, rgb.size, it, rms))
         return rgb, list(it), list(rms)
 
+    def decode_error_frc3(self, stream, rgb, max_iter: int = -1, rms_eps: float = 1e-5) -> dict:
+        """The decoded RGB error of an FRC3 colour container against `rgb` (frac_decode_error_frc3): the three plane
+        streams decoded at scale 1 on the device as decode_frc3 decodes them, converted and compared there pixel by
+        pixel, over the rectangle all three planes' g × g grids cover (include/fracenc.h states it); no RGB plane is
+        written and nothing decoded crosses PCIe.  No frame needs to be set on this engine.
+        rgb: a numpy uint8 [H, W, 3] array (uploaded), or a CUDA uint8 tensor [H, W, 3] with packed pixels (rows may
+        be strided; read in place on this engine's stream: frac_decode_error_frc3_device).
+        Returns a dict with sse (the sum of the three channels), channel_sse [R, G, B], pixels, psnr
+        (10·log10(255²·3·pixels / sse), inf at sse == 0), iterations and rms (lists of three, Y, U, V)."""
+        buf = np.frombuffer(stream, dtype=np.uint8)
+        sse, pixels = (C.c_uint64 * 3)(), C.c_uint64(0)
+        it, rms = (C.c_int * 3)(), (C.c_double * 3)()
+        ptr = buf.ctypes.data if len(buf) else None
+        if hasattr(rgb, "is_cuda"):
+            import torch
+
+            if not rgb.is_cuda or rgb.dtype != torch.uint8 or rgb.dim() != 3 or rgb.shape[2] != 3:
+                raise FracError("decode_error_frc3: rgb must be a numpy array or a CUDA uint8 tensor [H, W, 3]")
+            if rgb.stride(2) != 1 or rgb.stride(1) != 3:
+                raise FracError("decode_error_frc3: rgb must have packed pixels")
+            stride = _device_rows(rgb, 3 * int(rgb.shape[1]), "decode_error_frc3")
+            shape = (int(rgb.shape[0]), int(rgb.shape[1]))
+            torch.cuda.current_stream(rgb.device).synchronize()  # rgb must be ready before our stream reads it
+            fn, ref = lib().frac_decode_error_frc3_device, C.c_void_p(rgb.data_ptr())
+        else:
+            rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+            if rgb.ndim != 3 or rgb.shape[2] != 3:
+                raise FracError("decode_error_frc3: rgb must be [H, W, 3]")
+            stride, shape = 3 * rgb.shape[1], rgb.shape[:2]
+            fn, ref = lib().frac_decode_error_frc3, rgb.ctypes.data
+        # the library reads the container's frame from rgb, so rgb must have that frame's shape (a container the
+        # parser refuses is left to the call itself to refuse)
+        h = FracFrc3Info()
+        if lib().frac_frc3_info(ptr, len(buf), C.byref(h)) == 0 and tuple(shape) != (h.height, h.width):
+            raise FracError(f"decode_error_frc3: rgb is {shape[1]}x{shape[0]}, the container's frame "
+                            f"{h.width}x{h.height}")
+        self._check(fn(self._ctx, ptr, len(buf), ref, stride, max_iter, rms_eps, sse, C.byref(pixels), it, rms))
+        total = sum(sse)
+        return {"sse": total, "channel_sse": list(sse), "pixels": pixels.value,
+                "psnr": _psnr(total, 3 * pixels.value), "iterations": list(it), "rms": list(rms)}
+
+    def rate_candidates(self) -> np.ndarray:
+        """The rate state's candidates {0.0} ∪ {e(v)} as a float64 array, ascending and distinct
+        (frac_quadtree_rate_candidates): the list rate_quality bisects."""
+        n = C.c_size_t(0)
+        self._check(lib().frac_quadtree_rate_candidates(self._ctx, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.float64)
+        self._check(lib().frac_quadtree_rate_candidates(self._ctx, out.ctypes.data, len(out), C.byref(n)))
+        if n.value != len(out):
+            raise FracError(f"rate_candidates: {n.value} candidates, {len(out)} expected")
+        return out
+
     def device_results_ptr(self) -> int:
         """The device address of the last run's records; 0 when none are readable (no run yet, or a setter
         called since the last one)."""
@@ -1205,3 +1263,11 @@ def decode_color_stream(stream, scale: int = 1, device: int = 0, **kw):
     of its own (kw: max_iter, rms_eps, out).  Returns (rgb, [iterations]·3, [rms]·3)."""
     with Engine(device) as e:
         return e.decode_frc3(stream, scale, **kw)
+
+
+def color_stream_error(stream, rgb, device: int = 0, **kw):
+    """One call from an FRC3 colour container and an RGB frame to the decoded RGB error, beside
+    decode_color_stream: Engine.decode_error_frc3 on a context of its own (kw: max_iter, rms_eps).  Returns its
+    dict."""
+    with Engine(device) as e:
+        return e.decode_error_frc3(stream, rgb, **kw)

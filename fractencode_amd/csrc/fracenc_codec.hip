@@ -1203,60 +1203,93 @@ int frac_pack_frc3(const uint8_t* const planes[3], const size_t lens[3], uint32_
     return FRAC_OK;
 }
 
-// Both decode entry points: the three plane streams decoded on the context's stream into the planes of d_frc3
-// (Y at scale·W × scale·H, U and V at scale·(W/2) × scale·(H/2)), then converted into d_rgb, or (d_rgb NULL)
-// into d_frc3's RGB section, which is copied to h_rgb.
+// An FRC3 container opened for a decode at `scale`: the parsed headers and the geometry of the planes of d_frc3
+// (Y at scale·W × scale·H, U and V at scale·(W/2) × scale·(H/2), each at plane_pitch of its width); after
+// frc3_decode_planes also where they and the bytes asked for after them lie.
+struct Frc3Decode {
+    Frc3Info info;
+    Frc1Info h1[3];
+    Frq1Info hq[3];
+    uint32_t W = 0, H = 0, cw = 0, ch = 0, ys = 0, cs = 0;
+    size_t y_bytes = 0, c_bytes = 0;
+    uint8_t* d_plane[3] = {nullptr, nullptr, nullptr};
+    uint8_t* d_tail = nullptr;
+};
+
+// Everything a container's decode refuses by the container itself, before any launch.
+static int frc3_open(frac_ctx* c, const uint8_t* stream, size_t len, uint32_t scale, Frc3Decode* p)
+{
+    {
+        std::string msg;
+        if (frc3_parse(stream, len, &p->info, p->h1, p->hq, msg) != FRAC_OK)
+            return c->fail(FRAC_E_INVALID, msg);
+    }
+    const Frc3Info& info = p->info;
+    FRAC_TRY(check_ab_knobs(c));
+    if (scale < 1 || scale > 16 || (uint64_t)scale * info.width > 65535 || (uint64_t)scale * info.height > 65535)
+        return c->fail(FRAC_E_INVALID, "decode_frc3: scale must be in 1..16 and the scaled frame at most 65535 a side");
+    for (uint32_t k = 0; k < 3; ++k)
+        if (info.kind[k] == 2)
+            FRAC_TRY(frq1_decodable(c, p->hq[k]));
+    p->W = scale * info.width, p->H = scale * info.height;
+    p->cw = scale * (info.width / 2), p->ch = scale * (info.height / 2);
+    p->ys = plane_pitch(p->W), p->cs = plane_pitch(p->cw);
+    p->y_bytes = (size_t)p->ys * p->H, p->c_bytes = (size_t)p->cs * p->ch;
+    return FRAC_OK;
+}
+
+// The three plane streams of an opened container decoded on the context's stream from zero planes into d_frc3,
+// which also gets tail_bytes after the planes (d_tail).  Not synchronised.
+static int frc3_decode_planes(frac_ctx* c, const uint8_t* stream, Frc3Decode* p, uint32_t scale, int max_iter,
+                              double rms_eps, size_t tail_bytes, int* iterations, double* rms)
+{
+    FRAC_HIP(c, hipSetDevice(c->device));
+    FRAC_HIP(c, c->d_frc3.ensure(p->y_bytes + 2 * p->c_bytes + tail_bytes));
+    p->d_plane[0] = c->d_frc3.ptr;
+    p->d_plane[1] = p->d_plane[0] + p->y_bytes;
+    p->d_plane[2] = p->d_plane[1] + p->c_bytes;
+    p->d_tail = p->d_plane[2] + p->c_bytes;
+    for (uint32_t k = 0; k < 3; ++k) {
+        PlaneIO io;
+        io.d_out = p->d_plane[k];
+        io.d_pitch = k ? p->cs : p->ys;
+        const uint8_t* s = stream + p->info.offset[k];
+        int it = 0;
+        double r = 0.0;
+        if (p->info.kind[k] == 1)
+            FRAC_TRY(decode_frc1_parsed(c, p->h1[k], s, scale, max_iter, rms_eps, io, &it, &r));
+        else
+            FRAC_TRY(decode_frq1_parsed(c, p->hq[k], s, scale, max_iter, rms_eps, io, &it, &r));
+        if (iterations)
+            iterations[k] = it;
+        if (rms)
+            rms[k] = r;
+    }
+    return FRAC_OK;
+}
+
+// Both decode entry points: the planes of frc3_decode_planes converted into d_rgb, or (d_rgb NULL) into
+// d_frc3's RGB section after them, which is copied to h_rgb.
 static int decode_frc3_impl(frac_ctx* c, const uint8_t* stream, size_t len, uint32_t scale, int max_iter,
                             double rms_eps, void* d_rgb, uint8_t* h_rgb, uint32_t rgb_stride, size_t rgb_bytes,
                             int* iterations, double* rms)
 {
     if (!c)
         return FRAC_E_INVALID;
-    Frc3Info info;
-    Frc1Info h1[3];
-    Frq1Info hq[3];
-    {
-        std::string msg;
-        if (frc3_parse(stream, len, &info, h1, hq, msg) != FRAC_OK)
-            return c->fail(FRAC_E_INVALID, msg);
-    }
-    FRAC_TRY(check_ab_knobs(c));
-    if (scale < 1 || scale > 16 || (uint64_t)scale * info.width > 65535 || (uint64_t)scale * info.height > 65535)
-        return c->fail(FRAC_E_INVALID, "decode_frc3: scale must be in 1..16 and the scaled frame at most 65535 a side");
-    for (uint32_t k = 0; k < 3; ++k)
-        if (info.kind[k] == 2)
-            FRAC_TRY(frq1_decodable(c, hq[k]));
-    const uint32_t W = scale * info.width, H = scale * info.height;
-    const uint32_t cw = scale * (info.width / 2), ch = scale * (info.height / 2);
+    Frc3Decode p;
+    FRAC_TRY(frc3_open(c, stream, len, scale, &p));
+    const uint32_t W = p.W, H = p.H;
     if ((!d_rgb && !h_rgb) || rgb_stride < 3ull * W || rgb_bytes < (uint64_t)rgb_stride * (H - 1) + 3ull * W)
         return c->fail(FRAC_E_INVALID, "decode_frc3: rgb is NULL, its stride below 3·scale·W, or rgb_bytes short of "
                                        "the last row");
-    FRAC_HIP(c, hipSetDevice(c->device));
-    const uint32_t ys = plane_pitch(W), cs = plane_pitch(cw), rs = plane_pitch(3 * W);
-    const size_t y_bytes = (size_t)ys * H, c_bytes = (size_t)cs * ch;
-    FRAC_HIP(c, c->d_frc3.ensure(y_bytes + 2 * c_bytes + (d_rgb ? 0 : (size_t)rs * H)));
-    uint8_t* const d_plane[3] = {c->d_frc3.ptr, c->d_frc3.ptr + y_bytes, c->d_frc3.ptr + y_bytes + c_bytes};
-    for (uint32_t k = 0; k < 3; ++k) {
-        PlaneIO io;
-        io.d_out = d_plane[k];
-        io.d_pitch = k ? cs : ys;
-        const uint8_t* s = stream + info.offset[k];
-        int it = 0;
-        double r = 0.0;
-        if (info.kind[k] == 1)
-            FRAC_TRY(decode_frc1_parsed(c, h1[k], s, scale, max_iter, rms_eps, io, &it, &r));
-        else
-            FRAC_TRY(decode_frq1_parsed(c, hq[k], s, scale, max_iter, rms_eps, io, &it, &r));
-        if (iterations)
-            iterations[k] = it;
-        if (rms)
-            rms[k] = r;
-    }
+    const uint32_t rs = plane_pitch(3 * W);
+    FRAC_TRY(frc3_decode_planes(c, stream, &p, scale, max_iter, rms_eps, d_rgb ? 0 : (size_t)rs * H, iterations, rms));
     if (d_rgb)
-        return yuv_to_rgb_launch(c, d_plane[0], W, H, ys, d_plane[1], cs, d_plane[2], cs, cw, ch, d_rgb, rgb_stride);
-    uint8_t* stage = d_plane[2] + c_bytes;
-    FRAC_TRY(yuv_to_rgb_launch(c, d_plane[0], W, H, ys, d_plane[1], cs, d_plane[2], cs, cw, ch, stage, rs));
-    FRAC_TRY(copy_plane(c, h_rgb, rgb_stride, stage, rs, 3 * W, H, hipMemcpyDeviceToHost, c->stream));
+        return yuv_to_rgb_launch(c, p.d_plane[0], W, H, p.ys, p.d_plane[1], p.cs, p.d_plane[2], p.cs, p.cw, p.ch, d_rgb,
+                                 rgb_stride);
+    FRAC_TRY(yuv_to_rgb_launch(c, p.d_plane[0], W, H, p.ys, p.d_plane[1], p.cs, p.d_plane[2], p.cs, p.cw, p.ch,
+                               p.d_tail, rs));
+    FRAC_TRY(copy_plane(c, h_rgb, rgb_stride, p.d_tail, rs, 3 * W, H, hipMemcpyDeviceToHost, c->stream));
     FRAC_HIP(c, hipStreamSynchronize(c->stream));
     return FRAC_OK;
 }

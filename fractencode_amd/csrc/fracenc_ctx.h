@@ -301,7 +301,7 @@ struct frac_ctx {
     DBuf<uint32_t> d_frq_in, d_frq_nodes[2], d_frq_rank, d_frq_map;
     DBuf<uint4> d_frq_leaves;
     // frac_decode_frc3: the decoded Y, U and V planes (pitch plane_pitch of each width), which never leave the
-    // device, and after them the host variant's RGB staging rows
+    // device, and after them the host variant's RGB staging rows (frac_decode_error_frc3: the host's reference)
     DBuf<uint8_t> d_frc3;
     // quadtree: the per-level domain grids (geometry only) of the last frame size, by log2(n)
     uint32_t qt_w = 0, qt_h = 0;
@@ -387,10 +387,15 @@ struct frac_ctx {
     } rd;
     // decoded error (fracenc_quality.hip): the covered rectangle's sum and its block sums, the sum's pinned
     // landing place, the rate readers' stream on its way from the packer to the decoder, and the rate state's
-    // sorted keys on the host (the quality fit's candidates)
+    // sorted keys on the host (the quality fit's candidates); for a colour container the R, G and B sums and
+    // their landing place
     struct Quality {
-        DBuf<unsigned long long> d_total, d_block;
+        struct Rgb {
+            unsigned long long sse[3];
+        };
+        DBuf<unsigned long long> d_total, d_block, d_rgb_total;
         Pinned<unsigned long long> h_total;
+        Pinned<Rgb> h_rgb_total;
         PinnedBytes stream;
         std::vector<unsigned long long> skey;
     } quality;

@@ -13,6 +13,21 @@
 //                     workgroup's four waves in LDS: one atomic per workgroup.  Workgroups stride over the
 //                     blocks.  Nothing outside the covered rectangle is read: a unit lies in a block, a block in
 //                     the rectangle.
+//   yuv_rgb_sse       Σ(R − R_ref)², Σ(G − G_ref)², Σ(B − B_ref)² of three pitched u8 planes Y (full size), U and V
+//                     (half size) against a pitched packed-RGB reference over a rectangle rw × rh from the origin:
+//                     each pixel converted by fracenc::yuv_pixel (the decoders' conversion, fracenc_color.hip) and
+//                     compared in registers, so no RGB plane exists; nothing is written but the three u64 totals.
+//                     Integers only after the conversion, so no result depends on the order of the sums.  Two
+//                     paths, as the conversions have: <true> a lane takes 4 columns × 2 rows (one u16 of U and of
+//                     V, two dwords of Y, 2 × 3 dwords of the reference; rw % 4 == 0, rh even, pitches and bases
+//                     aligned: yuv_sse_fast_path), <false> a lane takes one 2 × 2 quad, with an odd trailing row or
+//                     column.  The grid is sized to the rectangle: a lane makes one trip, nothing strides.  A
+//                     lane's three sums (at most 8 · 255² each) are reduced as u32 over the wave by shuffles and
+//                     over the workgroup's four waves in LDS (at most 2048 · 255² < 2^27), then added as u64: at
+//                     most three atomics per workgroup, none for a zero sum.  The chroma cell of pixel (x, y) is
+//                     (x / 2, y / 2), which lies inside the chroma planes for every pixel of the rectangle (the
+//                     caller's rw <= 2 · chroma width, rh <= 2 · chroma height), so yuv2rgb_generic's clamp of the
+//                     chroma index is never live here and is not carried.
 // Included by fracenc_api.hip (after fracenc_codec.hip's decoders and fracenc_frq1pack.hip's packer, which the
 // entry points chain):
 //   frac_decode_error           parse as the decoders do, decode at scale 1 from a zero plane with a PlaneIO that
@@ -22,6 +37,11 @@
 //   frac_quadtree_rate_errors   per split distance the packer's stream (through a pinned buffer of the context:
 //                               the bytes frac_quadtree_rate_stream returns) into the same decode and comparison
 //   frac_quadtree_rate_quality  the stated bisection over the rate state's candidates, one such probe each
+//   frac_quadtree_rate_candidates  that list of candidates itself (rate_candidates_of, which the fit bisects)
+//   frac_decode_error_frc3      the container opened and its planes decoded as frac_decode_frc3 does
+//   (and _device)               (frc3_open, frc3_decode_planes), yuv_rgb_sse against the caller's RGB over the
+//                               rectangle all three planes' grids cover; the host variant's RGB is uploaded behind
+//                               the planes in d_frc3, rows as far apart as the caller's
 // The decoded plane, the frame and the leaves never cross PCIe.
 
 namespace {
@@ -95,6 +115,123 @@ __global__ void __launch_bounds__(256) plane_sse_blocks(PlaneSseArgs s)
         if (t)
             atomicAdd(s.total, t);
     }
+}
+
+struct YuvSseArgs {
+    const uint8_t* y; // the decoded planes
+    const uint8_t* u;
+    const uint8_t* v;
+    const uint8_t* rgb; // the reference, packed RGB
+    uint32_t ys, us, vs, rs; // their pitches
+    uint32_t rw, rh;         // the rectangle (both at least 1; rw <= 2 · chroma width, rh <= 2 · chroma height)
+    unsigned long long* total; // [3] the R, G and B sums are added here
+};
+
+// one converted pixel (yuv_pixel's three bytes) against the reference's r, g, b
+__device__ inline void rgb_sse_add(uint32_t px, uint32_t r, uint32_t g, uint32_t b, uint32_t acc[3])
+{
+    const int dr = (int)(px & 255u) - (int)r, dg = (int)((px >> 8) & 255u) - (int)g, db = (int)(px >> 16) - (int)b;
+    acc[0] += (uint32_t)(dr * dr);
+    acc[1] += (uint32_t)(dg * dg);
+    acc[2] += (uint32_t)(db * db);
+}
+
+inline bool yuv_sse_fast_path(const YuvSseArgs& a)
+{
+    auto al = [](const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) % n) == 0; };
+    return a.rw % 4 == 0 && a.rh % 2 == 0 && a.rs % 4 == 0 && a.ys % 4 == 0 && a.us % 2 == 0 && a.vs % 2 == 0 &&
+           al(a.rgb, 4) && al(a.y, 4) && al(a.u, 2) && al(a.v, 2);
+}
+
+// the lanes of the rectangle on either path: its 4 × 2 blocks, or its 2 × 2 quads (a trailing row or column
+// makes a quad of its own)
+inline uint64_t yuv_sse_lanes(const YuvSseArgs& a, bool fast)
+{
+    return fast ? (uint64_t)(a.rw / 4) * (a.rh / 2) : (uint64_t)((a.rw + 1) / 2) * ((a.rh + 1) / 2);
+}
+
+template <bool kFast>
+__global__ void __launch_bounds__(256) yuv_rgb_sse(YuvSseArgs s)
+{
+    __shared__ uint32_t part[4][3];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t acc[3] = {0, 0, 0};
+    // no lane leaves before the shuffles: one past the rectangle keeps its zeros
+    if (kFast) {
+        const uint32_t bw = s.rw / 4, bh = s.rh / 2;
+        if (t < (size_t)bw * bh) {
+            const uint32_t bx = (uint32_t)(t % bw), by = (uint32_t)(t / bw);
+            const uint32_t uu = *reinterpret_cast<const uint16_t*>(s.u + (size_t)by * s.us + 2 * (size_t)bx);
+            const uint32_t vv = *reinterpret_cast<const uint16_t*>(s.v + (size_t)by * s.vs + 2 * (size_t)bx);
+            const double up[2] = {(double)(uu & 255u) - 128.0, (double)(uu >> 8) - 128.0};
+            const double vp[2] = {(double)(vv & 255u) - 128.0, (double)(vv >> 8) - 128.0};
+#pragma unroll
+            for (int dy = 0; dy < 2; ++dy) {
+                const uint32_t y = 2 * by + dy;
+                const uint32_t yw = *reinterpret_cast<const uint32_t*>(s.y + (size_t)y * s.ys + 4 * (size_t)bx);
+                const uint32_t* ref = reinterpret_cast<const uint32_t*>(s.rgb + (size_t)y * s.rs + 12 * (size_t)bx);
+                const uint32_t w0 = ref[0], w1 = ref[1], w2 = ref[2];
+                // bytes: r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+                const uint32_t want[4][3] = {{w0 & 255u, (w0 >> 8) & 255u, (w0 >> 16) & 255u},
+                                             {w0 >> 24, w1 & 255u, (w1 >> 8) & 255u},
+                                             {(w1 >> 16) & 255u, w1 >> 24, w2 & 255u},
+                                             {(w2 >> 8) & 255u, (w2 >> 16) & 255u, w2 >> 24}};
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    rgb_sse_add(yuv_pixel((double)((yw >> (8 * k)) & 255u), up[k / 2], vp[k / 2]), want[k][0],
+                                want[k][1], want[k][2], acc);
+            }
+        }
+    } else {
+        const uint32_t qw = (s.rw + 1) / 2, qh = (s.rh + 1) / 2;
+        if (t < (size_t)qw * qh) {
+            const uint32_t qx = (uint32_t)(t % qw), qy = (uint32_t)(t / qw);
+            const double up = (double)s.u[(size_t)qy * s.us + qx] - 128.0, vp = (double)s.v[(size_t)qy * s.vs + qx] - 128.0;
+#pragma unroll
+            for (int dy = 0; dy < 2; ++dy) {
+                const uint32_t y = 2 * qy + dy;
+                if (y >= s.rh)
+                    break;
+#pragma unroll
+                for (int dx = 0; dx < 2; ++dx) {
+                    const uint32_t x = 2 * qx + dx;
+                    if (x >= s.rw)
+                        break;
+                    const uint8_t* p = s.rgb + (size_t)y * s.rs + 3 * (size_t)x;
+                    rgb_sse_add(yuv_pixel((double)s.y[(size_t)y * s.ys + x], up, vp), p[0], p[1], p[2], acc);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1)
+            acc[k] += __shfl_xor(acc[k], o, 64);
+        if (lane == 0)
+            part[wave][k] = acc[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const uint32_t k = threadIdx.x;
+        const uint32_t sum = part[0][k] + part[1][k] + part[2][k] + part[3][k];
+        if (sum)
+            atomicAdd(s.total + k, (unsigned long long)sum);
+    }
+}
+
+// The comparison enqueued on the context's stream, on the path the arguments allow.
+int yuv_rgb_sse_launch(frac_ctx* c, const YuvSseArgs& a)
+{
+    const bool fast = yuv_sse_fast_path(a);
+    const unsigned wgs = (unsigned)((yuv_sse_lanes(a, fast) + 255) / 256); // at most 65535² / 4 / 256 < 2^23
+    if (fast)
+        yuv_rgb_sse<true><<<wgs, 256, 0, c->stream>>>(a);
+    else
+        yuv_rgb_sse<false><<<wgs, 256, 0, c->stream>>>(a);
+    FRAC_HIP(c, hipGetLastError());
+    return FRAC_OK;
 }
 
 // what one stream's decode and comparison give
@@ -204,9 +341,150 @@ int rate_error_at(frac_ctx* c, uint32_t cbits, uint32_t bbits, double split, int
     return decode_error_of(c, Q.stream.ptr, *len, max_iter, eps, nullptr, 0, r);
 }
 
+// The rate state's candidates {0.0} ∪ {e(v)}, ascending and distinct, from its sorted keys: what the quality fit
+// bisects and frac_quadtree_rate_candidates returns.  The caller has run qtr_reader_checks.
+int rate_candidates_of(frac_ctx* c, std::vector<double>* cand)
+{
+    auto& R = c->rate;
+    auto& Q = c->quality;
+    Q.skey.resize(R.nkeys);
+    if (R.nkeys) {
+        FRAC_HIP(c, hipMemcpyAsync(Q.skey.data(), R.d_skey.ptr, (size_t)R.nkeys * sizeof(unsigned long long),
+                                   hipMemcpyDeviceToHost, c->stream));
+        FRAC_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    cand->clear();
+    cand->reserve((size_t)R.nkeys + 1);
+    bool zero = false;
+    auto push = [&](double v) {
+        if (cand->empty() || cand->back() != v)
+            cand->push_back(v);
+    };
+    for (unsigned long long k : Q.skey) {
+        const double v = qtr_val(k);
+        if (!zero && !(v < 0.0)) {
+            push(0.0);
+            zero = true;
+        }
+        push(v);
+    }
+    if (!zero)
+        push(0.0);
+    return FRAC_OK;
+}
+
+// what a container's decode and comparison give
+struct ColorError {
+    uint64_t sse[3] = {0, 0, 0}, pixels = 0;
+    int iterations[3] = {0, 0, 0};
+    double rms[3] = {0.0, 0.0, 0.0};
+};
+
+// what a g × g grid from the origin covers of w
+inline uint32_t covered(uint32_t w, uint32_t g) { return w - w % g; }
+
+// The container's planes decoded into d_frc3 and compared in RGB with the reference, which is d_rgb on the
+// device or h_rgb on the host (uploaded behind the planes); returns synchronised.
+int decode_error_frc3_of(frac_ctx* c, const uint8_t* stream, size_t len, const void* d_rgb, const uint8_t* h_rgb,
+                         uint32_t rgb_stride, int max_iter, double eps, ColorError* r)
+{
+    *r = ColorError{};
+    Frc3Decode p;
+    FRAC_TRY(frc3_open(c, stream, len, 1, &p));
+    if ((!d_rgb && !h_rgb) || rgb_stride < 3ull * p.W)
+        return c->fail(FRAC_E_INVALID, "decode_error_frc3: rgb is NULL or its stride below 3·W");
+    uint32_t rw = p.W, rh = p.H;
+    for (uint32_t k = 0; k < 3; ++k) {
+        const uint32_t g = p.info.kind[k] == 1 ? p.h1[k].range_size : p.hq[k].max_size;
+        if (g == 0)
+            return c->fail(FRAC_E_INVALID, "decode_error_frc3: a range size of zero");
+        rw = std::min(rw, k ? 2 * covered(p.cw, g) : covered(p.W, g));
+        rh = std::min(rh, k ? 2 * covered(p.ch, g) : covered(p.H, g));
+    }
+    r->pixels = (uint64_t)rw * rh;
+    // the host's rows stay rgb_stride apart, so one copy carries them: up to the rectangle's last pixel
+    const size_t ref_bytes = h_rgb && r->pixels ? (size_t)rgb_stride * (rh - 1) + 3 * (size_t)rw : 0;
+    FRAC_TRY(frc3_decode_planes(c, stream, &p, 1, max_iter, eps, ref_bytes, r->iterations, r->rms));
+    if (!r->pixels) {
+        FRAC_HIP(c, hipStreamSynchronize(c->stream));
+        return FRAC_OK;
+    }
+    auto& Q = c->quality;
+    FRAC_HIP(c, Q.d_rgb_total.ensure(3));
+    FRAC_HIP(c, Q.h_rgb_total.ensure());
+    FRAC_HIP(c, hipMemsetAsync(Q.d_rgb_total.ptr, 0, 3 * sizeof(unsigned long long), c->stream));
+    if (h_rgb)
+        FRAC_HIP(c, hipMemcpyAsync(p.d_tail, h_rgb, ref_bytes, hipMemcpyHostToDevice, c->stream));
+    YuvSseArgs a{};
+    a.y = p.d_plane[0], a.u = p.d_plane[1], a.v = p.d_plane[2];
+    a.ys = p.ys, a.us = a.vs = p.cs;
+    a.rgb = h_rgb ? p.d_tail : static_cast<const uint8_t*>(d_rgb);
+    a.rs = rgb_stride;
+    a.rw = rw, a.rh = rh;
+    a.total = Q.d_rgb_total.ptr;
+    FRAC_TRY(yuv_rgb_sse_launch(c, a));
+    FRAC_HIP(c, hipMemcpyAsync(Q.h_rgb_total.ptr, Q.d_rgb_total.ptr, 3 * sizeof(unsigned long long),
+                               hipMemcpyDeviceToHost, c->stream));
+    FRAC_HIP(c, hipStreamSynchronize(c->stream));
+    for (uint32_t k = 0; k < 3; ++k)
+        r->sse[k] = Q.h_rgb_total->sse[k];
+    return FRAC_OK;
+}
+
+int decode_error_frc3_out(frac_ctx* c, const uint8_t* stream, size_t len, const void* d_rgb, const uint8_t* h_rgb,
+                          uint32_t rgb_stride, int max_iter, double eps, uint64_t sse[3], uint64_t* pixels,
+                          int iterations[3], double rms[3])
+{
+    if (!c)
+        return FRAC_E_INVALID;
+    ColorError r;
+    FRAC_TRY(decode_error_frc3_of(c, stream, len, d_rgb, h_rgb, rgb_stride, max_iter, eps, &r));
+    for (uint32_t k = 0; k < 3; ++k) {
+        if (sse)
+            sse[k] = r.sse[k];
+        if (iterations)
+            iterations[k] = r.iterations[k];
+        if (rms)
+            rms[k] = r.rms[k];
+    }
+    if (pixels)
+        *pixels = r.pixels;
+    return FRAC_OK;
+}
+
 } // namespace
 
 extern "C" {
+
+int frac_decode_error_frc3(frac_ctx* c, const uint8_t* stream, size_t len, const uint8_t* rgb, uint32_t rgb_stride,
+                           int max_iter, double rms_eps, uint64_t sse[3], uint64_t* pixels, int iterations[3],
+                           double rms[3])
+{
+    return decode_error_frc3_out(c, stream, len, nullptr, rgb, rgb_stride, max_iter, rms_eps, sse, pixels, iterations,
+                                 rms);
+}
+
+int frac_decode_error_frc3_device(frac_ctx* c, const uint8_t* stream, size_t len, const void* d_rgb,
+                                  uint32_t rgb_stride, int max_iter, double rms_eps, uint64_t sse[3], uint64_t* pixels,
+                                  int iterations[3], double rms[3])
+{
+    return decode_error_frc3_out(c, stream, len, d_rgb, nullptr, rgb_stride, max_iter, rms_eps, sse, pixels,
+                                 iterations, rms);
+}
+
+int frac_quadtree_rate_candidates(frac_ctx* c, double* out, size_t cap, size_t* n_out)
+{
+    if (!c)
+        return FRAC_E_INVALID;
+    FRAC_TRY(qtr_reader_checks(c, "quadtree rate candidates", 2, 2));
+    std::vector<double> cand;
+    FRAC_TRY(rate_candidates_of(c, &cand));
+    if (n_out)
+        *n_out = cand.size();
+    if (out)
+        std::memcpy(out, cand.data(), std::min(cand.size(), cap) * sizeof(double));
+    return FRAC_OK;
+}
 
 int frac_decode_error(frac_ctx* c, const uint8_t* stream, size_t len, int max_iter, double rms_eps, uint64_t* sse,
                       uint64_t* pixels, uint64_t* block_sse, size_t block_cap, size_t* n_blocks, int* iterations,
@@ -258,32 +536,8 @@ int frac_quadtree_rate_quality(frac_ctx* c, uint32_t cbits, uint32_t bbits, uint
     if (!c)
         return FRAC_E_INVALID;
     FRAC_TRY(qtr_reader_checks(c, "quadtree rate quality", cbits, bbits));
-    auto& R = c->rate;
-    auto& Q = c->quality;
-    // the candidates {0.0} ∪ {e(v)}, ascending and distinct, from the state's sorted keys
-    Q.skey.resize(R.nkeys);
-    if (R.nkeys) {
-        FRAC_HIP(c, hipMemcpyAsync(Q.skey.data(), R.d_skey.ptr, (size_t)R.nkeys * sizeof(unsigned long long),
-                                   hipMemcpyDeviceToHost, c->stream));
-        FRAC_HIP(c, hipStreamSynchronize(c->stream));
-    }
     std::vector<double> cand;
-    cand.reserve((size_t)R.nkeys + 1);
-    bool zero = false;
-    auto push = [&](double v) {
-        if (cand.empty() || cand.back() != v)
-            cand.push_back(v);
-    };
-    for (unsigned long long k : Q.skey) {
-        const double v = qtr_val(k);
-        if (!zero && !(v < 0.0)) {
-            push(0.0);
-            zero = true;
-        }
-        push(v);
-    }
-    if (!zero)
-        push(0.0);
+    FRAC_TRY(rate_candidates_of(c, &cand));
     const size_t m = cand.size();
     struct Probe {
         StreamError r;

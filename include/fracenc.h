@@ -667,6 +667,44 @@ int frac_decode_frc3_device(frac_ctx* ctx, const uint8_t* stream, size_t len, ui
                             double rms_eps, void* d_rgb, uint32_t rgb_stride, size_t rgb_bytes, int iterations[3],
                             double rms[3]);
 
+/* ---- colour quality: the RGB error of an FRC3 container, and a rate state's candidates ----
+ * These three symbols were added after ABI 9 without changing FRAC_ABI_VERSION: probe for them by name
+ * (dlsym) when the library may be older.
+ *
+ * frac_decode_error_frc3 measures what a viewer of a colour stream gets, as frac_decode_error does for one
+ * plane: the container is parsed and validated as frac_frc3_info does, its three plane streams are decoded at
+ * scale 1 from zero planes exactly as frac_decode_frc3 decodes them, and the decoded planes are converted pixel by
+ * pixel as frac_yuv_to_rgb_device converts them and compared, in registers, with the packed RGB reference `rgb`
+ * (width × height pixels, rows rgb_stride bytes apart).  No RGB plane is written and nothing decoded crosses PCIe.
+ * The reference is an argument: no frame needs to be set on ctx, and any context can make the call.
+ * Covered rectangle: with g_k plane k's FRC1 range_size or FRQ1 max_size, cov(w, g) = w − w % g, W and H the
+ * container's width and height,
+ *     rw = min(cov(W, g_Y), 2·cov(W/2, g_U), 2·cov(W/2, g_V)),  rh likewise from H,
+ * the pixels from the origin that all three planes' grids cover.  *pixels = rw·rh; sse[0..2] are Σ(R − R_ref)²,
+ * Σ(G − G_ref)² and Σ(B − B_ref)² over the rectangle, exact unsigned 64-bit integers.  A plane smaller than its g
+ * gives pixels = 0 and all sums 0: the decode still runs (iterations and rms are reported), nothing is launched
+ * for the comparison.  A record or leaf without a domain leaves its pixels at zero and is counted like any other.
+ * iterations[k] and rms[k] are what frac_decode_frc3 reports for plane k.  Every output pointer may be NULL.
+ * FRAC_E_INVALID, before any launch: a NULL rgb; rgb_stride < 3·W; a container that frac_frc3_info refuses; a
+ * plane stream that the decoders refuse.  The call returns synchronised.  It is a reader, like frac_decode_error:
+ * a run's readable results, the rate state and the tuple sink stay as they were; only the decoder's buffers and
+ * the container decoder's planes are touched.
+ * frac_decode_error_frc3: rgb is host memory, read up to the rectangle's last pixel and uploaded into a buffer of
+ * the context.  _device: d_rgb is a device pointer, read on the ctx stream.
+ *
+ * frac_quadtree_rate_candidates is a rate reader, with frac_quadtree_rate_sizes' state rules (FRAC_E_STATE
+ * without a readable rate state; it searches nothing and leaves the state and a run's readable results alone).
+ * It returns the state's candidates {0.0} ∪ {e(v)}, ascending and distinct: the very list c[0] < … < c[m − 1]
+ * that frac_quadtree_rate_quality bisects.  *n_out = m (may be NULL); min(m, cap) entries are written; out may
+ * be NULL to query the count.  An empty state (no level-0 ranges) gives the single candidate 0.0. */
+int frac_decode_error_frc3(frac_ctx* ctx, const uint8_t* stream, size_t len, const uint8_t* rgb, uint32_t rgb_stride,
+                           int max_iter, double rms_eps, uint64_t sse[3], uint64_t* pixels, int iterations[3],
+                           double rms[3]);
+int frac_decode_error_frc3_device(frac_ctx* ctx, const uint8_t* stream, size_t len, const void* d_rgb,
+                                  uint32_t rgb_stride, int max_iter, double rms_eps, uint64_t sse[3],
+                                  uint64_t* pixels, int iterations[3], double rms[3]);
+int frac_quadtree_rate_candidates(frac_ctx* ctx, double* out, size_t cap, size_t* n_out);
+
 /* ---- host helpers (no device needed) ------------------------------------ */
 /* createUniformGrid (image/partition2.hpp:109-135): returns the item count and
  * writes min(count, cap) items (categories -1).  Returns 0 where the reference's loop has no

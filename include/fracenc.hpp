@@ -348,6 +348,43 @@ public:
                                          &q.split_distance, &q.bytes, &q.leaves, &q.sse, &q.probes));
         return q;
     }
+    // the rate state's candidates {0.0} ∪ {e(v)}, ascending and distinct: the list rateQuality bisects
+    // (frac_quadtree_rate_candidates)
+    std::vector<double> rateCandidates()
+    {
+        size_t n = 0;
+        check(frac_quadtree_rate_candidates(ctx_, nullptr, 0, &n));
+        std::vector<double> c(n);
+        check(frac_quadtree_rate_candidates(ctx_, c.data(), c.size(), &n));
+        c.resize(std::min(n, c.size()));
+        return c;
+    }
+    // The decoded RGB error of an FRC3 colour container against a packed RGB reference of the container's frame,
+    // rows rgb_stride bytes apart (frac_decode_error_frc3; device = true: rgb is a device pointer, read on the
+    // context's stream, frac_decode_error_frc3_device): the R, G and B sums over the rectangle all three planes'
+    // grids cover, its area, and per plane (Y, U, V) the iteration count and the final rms.
+    struct ColorError {
+        uint64_t channel_sse[3], pixels;
+        int iterations[3];
+        double rms[3];
+        uint64_t sse() const { return channel_sse[0] + channel_sse[1] + channel_sse[2]; }
+        // 10·log10(255²·3·pixels / sse); +inf at sse == 0
+        double psnr() const
+        {
+            return sse() ? 10.0 * std::log10(255.0 * 255.0 * 3.0 * (double)pixels / (double)sse())
+                         : std::numeric_limits<double>::infinity();
+        }
+    };
+    ColorError decodeErrorFrc3(const uint8_t* stream, size_t len, const void* rgb, uint32_t rgb_stride,
+                               bool device = false, int max_iter = -1, double rms_eps = 1e-5)
+    {
+        ColorError r{};
+        check(device ? frac_decode_error_frc3_device(ctx_, stream, len, rgb, rgb_stride, max_iter, rms_eps,
+                                                     r.channel_sse, &r.pixels, r.iterations, r.rms)
+                     : frac_decode_error_frc3(ctx_, stream, len, static_cast<const uint8_t*>(rgb), rgb_stride, max_iter,
+                                              rms_eps, r.channel_sse, &r.pixels, r.iterations, r.rms));
+        return r;
+    }
     // Decoder2::decode (encode/Encoder2.hpp:67-88); plane holds the caller's initial target
     // (main.cpp zeroes it) and receives the result.  Returns {iterations, rms}.
     std::pair<int, double> decode(const std::vector<frac_encode_item>& items, uint32_t w, uint32_t h,
