@@ -274,6 +274,10 @@ def lib() -> C.CDLL:
                                                     C.POINTER(C.c_uint64), C.POINTER(C.c_int),
                                                     C.POINTER(C.c_double)]),
             "frac_quadtree_rate_candidates": (i32, [vp, vp, sz, C.POINTER(sz)]),
+            "frac_decode_inter": (i32, [vp, vp, sz, u32, vp, vp, sz]),
+            "frac_decode_inter_device": (i32, [vp, vp, sz, u32, vp, u32, vp, u32, sz]),
+            "frac_inter_error": (i32, [vp, vp, sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+            "frac_set_planes_device": (i32, [vp, vp, u32, u32, u32, vp, u32, u32, u32]),
             "frac_uniform_grid": (sz, [u32, u32, u32, u32, vp, sz]),
             "frac_uniform_grid2": (sz, [u32, u32, u32, u32, u32, u32, vp, sz]),
             "frac_classify": (i32, [vp, u32, u32, u32, vp, sz]),
@@ -508,6 +512,12 @@ def _device_rows(t, width_bytes: int, what: str) -> int:
     return stride
 
 
+def _stream_frame(stream) -> tuple[int, int]:
+    """(width, height) of an FRC1 or FRQ1 stream, told apart by its magic (frac_frc1_info / frac_frq1_info)."""
+    h = frq1_info(stream) if bytes(memoryview(stream)[:4]) == b"FRQ1" else frc1_info(stream)
+    return h["width"], h["height"]
+
+
 def transform_index(n: int, t: int, pix: int) -> int:
     return lib().frac_transform_index(n, t, pix)
 
@@ -634,7 +644,26 @@ class Engine:
         self._check(lib().frac_set_frame_async(self._ctx, C.c_void_p(plane.ctypes.data), plane.shape[1],
                                                plane.shape[0], plane.strides[0]))
 
-    def set_planes(self, source: np.ndarray, target: np.ndarray) -> None:
+    def set_planes(self, source, target) -> None:
+        """Domains on `source`, ranges on `target` (frac_set_planes): two numpy uint8 [H, W] planes, or two CUDA
+        uint8 tensors (rows may be strided), copied device to device (frac_set_planes_device)."""
+        if any(hasattr(p, "is_cuda") and p.is_cuda for p in (source, target)):
+            import torch
+
+            for p in (source, target):
+                if not (hasattr(p, "is_cuda") and p.is_cuda) or p.dtype != torch.uint8 or p.dim() != 2:
+                    raise FracError("set_planes: device planes must both be 2-D CUDA uint8 tensors")
+                if p.stride(1) != 1 and p.shape[1] > 1:
+                    raise FracError("set_planes: device plane rows must be contiguous (stride(1) == 1)")
+            ss = _device_rows(source, int(source.shape[1]), "set_planes")
+            ts = _device_rows(target, int(target.shape[1]), "set_planes")
+            # the library copies on its own stream: work still pending on torch's current stream lands first
+            torch.cuda.current_stream(source.device).synchronize()
+            self._check(lib().frac_set_planes_device(self._ctx, C.c_void_p(source.data_ptr()), source.shape[1],
+                                                     source.shape[0], ss, C.c_void_p(target.data_ptr()),
+                                                     target.shape[1], target.shape[0], ts))
+            self._frame_wh = (int(source.shape[1]), int(source.shape[0]))  # a refused call leaves it as it was
+            return
         self._frame_wh = (int(source.shape[1]), int(source.shape[0]))
         s = np.ascontiguousarray(source, dtype=np.uint8)
         t = np.ascontiguousarray(target, dtype=np.uint8)
@@ -770,6 +799,59 @@ class Engine:
         self._check(lib().frac_decode_frq1(self._ctx, buf.ctypes.data, len(buf), scale, max_iter, rms_eps,
                                            plane.ctypes.data, plane.size, C.byref(it), C.byref(rms)))
         return plane, it.value, rms.value
+
+    def decode_inter(self, stream, ref, scale: int = 1, out=None):
+        """An FRC1 or FRQ1 stream applied once to the reference plane `ref` (frac_decode_inter): the plane is a copy
+        of `ref` in which every record or leaf with a domain has written its range from its domain patch in `ref`,
+        every coordinate and size multiplied by `scale`.  One pass: no iterations, no rms.  `ref` is scale·H ×
+        scale·W: a numpy uint8 array (the host call; a numpy plane is returned), or a CUDA uint8 tensor, read in
+        place (frac_decode_inter_device; rows may be strided); the pixels then go into `out`, a CUDA uint8 tensor
+        of that shape that does not overlap `ref` (rows may be strided; the bytes between them stay), or into a new
+        tensor.  Returns the plane."""
+        if not 1 <= scale <= 16:
+            raise FracError("decode_inter: scale must be in 1..16")
+        W, H = _stream_frame(stream)
+        W, H = scale * W, scale * H
+        buf = np.frombuffer(stream, dtype=np.uint8)
+        if hasattr(ref, "is_cuda") and ref.is_cuda:
+            import torch
+
+            if out is None:
+                out = torch.empty((H, W), dtype=torch.uint8, device=ref.device)
+            for name, t in (("ref", ref), ("out", out)):
+                if not (hasattr(t, "is_cuda") and t.is_cuda) or t.dtype != torch.uint8 or t.dim() != 2:
+                    raise FracError(f"decode_inter: {name} must be a 2-D CUDA uint8 tensor")
+                if tuple(t.shape) != (H, W):
+                    raise FracError(f"decode_inter: {name} must be {H}x{W}")
+                if t.stride(1) != 1 and t.shape[1] > 1:
+                    raise FracError(f"decode_inter: {name} rows must be contiguous (stride(1) == 1)")
+            rs, ps = _device_rows(ref, W, "decode_inter"), _device_rows(out, W, "decode_inter")
+            torch.cuda.current_stream(ref.device).synchronize()  # pending work on ref and out lands first
+            self._check(lib().frac_decode_inter_device(self._ctx, buf.ctypes.data, len(buf), scale,
+                                                       C.c_void_p(ref.data_ptr()), rs, C.c_void_p(out.data_ptr()), ps,
+                                                       ps * (H - 1) + W))
+            self.sync()
+            return out
+        if out is not None:
+            raise FracError("decode_inter: out goes with a CUDA ref")
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        if ref.shape != (H, W):
+            raise FracError(f"decode_inter: ref must be {H}x{W}")
+        plane = np.zeros((H, W), np.uint8)
+        self._check(lib().frac_decode_inter(self._ctx, buf.ctypes.data, len(buf), scale, ref.ctypes.data,
+                                            plane.ctypes.data, plane.size))
+        return plane
+
+    def inter_error(self, stream) -> dict:
+        """The error of an FRC1 or FRQ1 stream applied once, at scale 1, to the plane the domains lie on, against
+        the plane the ranges lie on (frac_inter_error): after set_planes(source, target) the exact decoded error of
+        an inter-coded frame, after set_frame the quantized collage error of an ordinary stream.  Over
+        decode_error's covered rectangle; nothing crosses PCIe.  Returns a dict with sse, pixels and psnr."""
+        buf = np.frombuffer(stream, dtype=np.uint8)
+        sse, pixels = C.c_uint64(0), C.c_uint64(0)
+        self._check(lib().frac_inter_error(self._ctx, buf.ctypes.data if len(buf) else None, len(buf), C.byref(sse),
+                                           C.byref(pixels)))
+        return {"sse": sse.value, "pixels": pixels.value, "psnr": _psnr(sse.value, pixels.value)}
 
     def _frq1_buffer(self, max_size: int, min_size: int, contrast_bits: int, brightness_bits: int):
         """A byte buffer kept across calls that holds any FRQ1 stream of this frame at these sizes and widths: every
@@ -1271,3 +1353,113 @@ def color_stream_error(stream, rgb, device: int = 0, **kw):
     dict."""
     with Engine(device) as e:
         return e.decode_error_frc3(stream, rgb, **kw)
+
+
+def decode_inter_stream(stream, ref, scale: int = 1, device: int = 0):
+    """One call from an inter-coded stream and its reference plane to pixels, beside decode_stream:
+    Engine.decode_inter on a context of its own.  Returns the plane."""
+    with Engine(device) as e:
+        return e.decode_inter(stream, ref, scale)
+
+
+class SequenceEncoder:
+    """A closed-loop encoder of a sequence of planes of one size: every `gop`-th frame, starting with the first, is
+    an I frame (an ordinary quadtree stream, decoded iteratively), every other one a P frame whose domains lie on
+    the previous frame's reconstruction, which the decoder has too: frame k is coded against what frame k − 1
+    decodes to, so the error does not drift.
+
+    An I frame is set_frame, encode_quadtree_stream and decode_frq1; its reconstruction is uploaded into a device
+    tensor: one plane crosses PCIe per I frame, down and up again (the iterative decoders have no device output).
+    A P frame stays on the device: set_planes(reconstruction, frame), encode_quadtree_stream(host_pack=False),
+    decode_inter(stream, reconstruction, out=spare), and the two reconstruction tensors swap.  A numpy frame is
+    uploaded first."""
+
+    def __init__(self, device: int = 0, transforms: int = 4, max_size: int = 16, min_size: int = 4,
+                 split_distance: float = 10.0, gop: int = 8, contrast_bits: int = 5, brightness_bits: int = 7,
+                 use_classifier: bool = False):
+        if gop < 1:
+            raise FracError("SequenceEncoder: gop must be at least 1")
+        self._e = Engine(device, transforms, use_classifier)
+        self._device = device
+        self._qt = (max_size, min_size, split_distance, contrast_bits, brightness_bits)
+        self._gop = gop
+        self._frames = []
+        self._wh = None
+        self._rec = self._spare = None
+
+    def close(self) -> None:
+        self._e.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def push(self, plane):
+        """The next frame (numpy uint8 [H, W] or a CUDA uint8 tensor) → (kind, stream), kind "I" or "P"."""
+        import torch
+
+        wh = (int(plane.shape[1]), int(plane.shape[0]))
+        if self._wh is None:
+            self._wh = wh
+            dev = torch.device("cuda", self._device)
+            self._rec = torch.empty((wh[1], wh[0]), dtype=torch.uint8, device=dev)
+            self._spare = torch.empty_like(self._rec)
+        elif wh != self._wh:
+            raise FracError(f"SequenceEncoder: a frame of {wh[0]}x{wh[1]} in a sequence of {self._wh[0]}x{self._wh[1]}")
+        e = self._e
+        if len(self._frames) % self._gop == 0:
+            kind = "I"
+            e.set_frame(plane)
+            stream, _ = e.encode_quadtree_stream(*self._qt)
+            rec, _, _ = e.decode_frq1(stream)
+            self._rec.copy_(torch.from_numpy(rec))
+        else:
+            kind = "P"
+            if not (hasattr(plane, "is_cuda") and plane.is_cuda):
+                plane = torch.from_numpy(np.ascontiguousarray(plane, dtype=np.uint8)).to(self._rec.device)
+            e.set_planes(self._rec, plane)
+            stream, _ = e.encode_quadtree_stream(*self._qt, host_pack=False)
+            e.decode_inter(stream, self._rec, out=self._spare)
+            self._rec, self._spare = self._spare, self._rec
+        self._frames.append((kind, stream))
+        return kind, stream
+
+    def reconstruction(self):
+        """What a decoder makes of the frames pushed so far: the last frame's plane, a CUDA uint8 tensor that the
+        next push() overwrites or retires (clone it to keep it)."""
+        if not self._frames:
+            raise FracError("SequenceEncoder: no frame pushed")
+        return self._rec
+
+    def pack(self) -> bytes:
+        """The frames pushed so far as one FRCS container (codec.pack_sequence)."""
+        from . import codec
+
+        if self._wh is None:
+            raise FracError("SequenceEncoder: no frame pushed")
+        return codec.pack_sequence(self._frames, *self._wh)
+
+
+def decode_sequence(data, scale: int = 1, device: int = 0):
+    """An FRCS container (codec.unpack_sequence) to its planes, a list of numpy uint8 [scale·H, scale·W] arrays:
+    I frames through decode_frq1 / decode_frc1, P frames through decode_inter against the previous output, which
+    stays on the device between frames."""
+    import torch
+
+    from . import codec
+
+    frames, _ = codec.unpack_sequence(data)
+    planes, prev = [], None
+    with Engine(device) as e:
+        for kind, stream in frames:
+            if kind == "I":
+                fn = e.decode_frq1 if stream[:4] == b"FRQ1" else e.decode_frc1
+                plane = fn(stream, scale)[0]
+                prev = torch.from_numpy(plane).to(torch.device("cuda", device))
+            else:
+                prev = e.decode_inter(stream, prev, scale)
+                plane = prev.cpu().numpy()
+            planes.append(plane)
+    return planes

@@ -77,6 +77,22 @@ The Y stream's frame is width × height, the U and V streams' (width/2) × (heig
 planes (image/ImageIO.cpp:43-58).  frac_decode_frc3 (Engine.decode_frc3) decodes the three planes on the
 device and converts them to packed RGB there (ImageIO::yuv2rgb, ImageIO.cpp:68-84); frac_pack_frc3 /
 frac_frc3_info write and parse the container; pack_color_stream / unpack_color_stream are the host restatement.
+
+Sequence container layout ("FRCS", little-endian): the frames of one closed-loop sequence (SequenceEncoder) in
+one buffer.  An I frame is an ordinary stream, decoded iteratively; a P frame's records read their domains in the
+previous decoded frame and are applied to it once (frac_decode_inter).  The streams themselves are unchanged FRC1 /
+FRQ1 bytes: only this container says which is which.  Host only (pack_sequence / unpack_sequence)::
+
+    0   char[4]  magic "FRCS"
+    4   u16      version (1)
+    6   u16      flags (reserved, 0)
+    8   u32      width, height          every frame's; both in 1..65535
+    16  u32      n_frames
+    20  per frame, 8 bytes: u8 kind ('I' = 0x49 or 'P' = 0x50), three zero bytes, u32 length of its stream
+    20 + 8·n_frames  the streams in frame order, each a complete FRC1 or FRQ1 stream of a width × height frame,
+        each zero-padded to a multiple of 8 bytes
+
+The first frame is an I frame.
 """
 from __future__ import annotations
 
@@ -560,3 +576,84 @@ def unpack_color_stream(buf: bytes) -> tuple[list[bytes], dict]:
     h["total_bytes"] = pos
     h["kind"] = _check_color_planes(streams, width, height)
     return streams, h
+
+
+# ---- FRCS: the sequence container (layout in the module docstring) ------------------------------
+
+SEQ_MAGIC = b"FRCS"
+SEQ_HEADER = struct.Struct("<4sHHII")
+assert SEQ_HEADER.size == 16
+SEQ_COUNT = struct.Struct("<I")
+SEQ_FRAME = struct.Struct("<B3sI")
+SEQ_KINDS = {"I": 0x49, "P": 0x50}
+
+
+def _check_sequence_frames(frames, width: int, height: int) -> None:
+    for k, (kind, s) in enumerate(frames):
+        if kind not in SEQ_KINDS:
+            raise ValueError(f"FRCS: frame {k}: kind {kind!r} is neither I nor P")
+        if k == 0 and kind != "I":
+            raise ValueError("FRCS: the first frame must be an I frame")
+        _, w, h = _plane_stream_frame(bytes(s), f"frame {k}")
+        if (w, h) != (width, height):
+            raise ValueError(f"FRCS: frame {k}'s stream is {w}x{h}, the sequence {width}x{height}")
+
+
+def pack_sequence(frames, width: int, height: int) -> bytes:
+    """[(kind, stream), ...] with kind "I" or "P" and each stream a complete FRC1 or FRQ1 stream of a
+    width × height frame, as one FRCS container."""
+    frames = [(kind, bytes(s)) for kind, s in frames]
+    if not (1 <= width <= 65535 and 1 <= height <= 65535):
+        raise ValueError("FRCS: width and height must be in 1..65535")
+    _check_sequence_frames(frames, width, height)
+    out = SEQ_HEADER.pack(SEQ_MAGIC, VERSION, 0, width, height) + SEQ_COUNT.pack(len(frames))
+    for kind, s in frames:
+        out += SEQ_FRAME.pack(SEQ_KINDS[kind], bytes(3), len(s))
+    for _, s in frames:
+        out += s + bytes(-len(s) % 8)
+    return out
+
+
+def unpack_sequence(buf: bytes) -> tuple[list[tuple[str, bytes]], dict]:
+    """FRCS → ([(kind, stream), ...] without the padding, header dict: width, height, flags, frames, and per
+    frame offset and length in bytes from the start of the container, total_bytes).  Every frame stream is
+    checked by its own unpacker and against the sequence's frame."""
+    buf = bytes(buf)
+    if len(buf) < SEQ_HEADER.size + SEQ_COUNT.size:
+        raise ValueError("FRCS: truncated header")
+    magic, version, flags, width, height = SEQ_HEADER.unpack_from(buf, 0)
+    if magic != SEQ_MAGIC or version != VERSION:
+        raise ValueError("FRCS: bad magic or version")
+    if flags:
+        raise ValueError("FRCS: the flags are not zero")
+    if not (1 <= width <= 65535 and 1 <= height <= 65535):
+        raise ValueError("FRCS: width and height must be in 1..65535")
+    (n,) = SEQ_COUNT.unpack_from(buf, SEQ_HEADER.size)
+    pos = SEQ_HEADER.size + SEQ_COUNT.size
+    if len(buf) - pos < n * SEQ_FRAME.size:
+        raise ValueError("FRCS: the frame table runs past the end of the container")
+    names = {v: k for k, v in SEQ_KINDS.items()}
+    table = []
+    for k in range(n):
+        kind, pad, length = SEQ_FRAME.unpack_from(buf, pos)
+        if any(pad):
+            raise ValueError("FRCS: a padding byte is not zero")
+        if kind not in names:
+            raise ValueError(f"FRCS: frame {k}: kind {kind:#x} is neither I nor P")
+        table.append((names[kind], length))
+        pos += SEQ_FRAME.size
+    h = {"width": width, "height": height, "flags": flags, "frames": n, "offset": [], "length": []}
+    frames = []
+    for kind, length in table:
+        padded = length + (-length % 8)
+        if len(buf) - pos < padded:
+            raise ValueError("FRCS: a frame section runs past the end of the container")
+        if any(buf[pos + length:pos + padded]):
+            raise ValueError("FRCS: a padding byte is not zero")
+        frames.append((kind, buf[pos:pos + length]))
+        h["offset"].append(pos)
+        h["length"].append(length)
+        pos += padded
+    h["total_bytes"] = pos
+    _check_sequence_frames(frames, width, height)
+    return frames, h

@@ -5,10 +5,11 @@
 //   fracenc_plan.hip     validation, device bucketing, prepare(): work lists and buffers per engine
 //   fracenc_launch.hip   variant selection, the engines' launch paths, the fp32 fallback
 //   fracenc_quadtree.hip quadtree frames, host- and device-planned
-//   fracenc_codec.hip    decode, FRC1 and FRQ1 pack / parse / decode, colour conversion
+//   fracenc_codec.hip    decode, FRC1 and FRQ1 pack / parse / decode, inter-frame decode, colour conversion
 //   fracenc_qtrate.hip   quadtree rate sweep: the full tree searched once, sizes, fit and leaves per threshold
 //   fracenc_qtrd.hip     rate–distortion-optimal partitions of that tree: sizes, fit, leaves and stream per multiplier
-//   fracenc_quality.hip  decoded error of a stream against the frame; the rate state's errors and quality fit
+//   fracenc_quality.hip  decoded error of a stream against the frame; the rate state's errors and quality fit;
+//                        the error of a stream applied once to the other plane
 //
 // Host logic mirrored from the reference:
 //   classifier gating      encode/Classifier2.cpp:8-81   (categories computed on the host,
@@ -37,6 +38,7 @@
 #include "fracenc_stream.hip"
 #include "fracenc_frc1dec.hip"
 #include "fracenc_frq1dec.hip"
+#include "fracenc_inter.hip"
 #include "fracenc_tp.hip"
 #include "fracenc_tpsort.hip"
 #include "fracenc_gen.hip"
@@ -610,6 +612,35 @@ static int set_frame_device(frac_ctx* c, const void* d_plane, uint32_t w, uint32
 int frac_set_frame_device(frac_ctx* c, const void* d_plane, uint32_t w, uint32_t h, uint32_t stride)
 {
     return set_frame_device(c, d_plane, w, h, stride, true);
+}
+
+// frac_set_planes with both planes already on the device: copied as frac_set_frame_device copies one, into the
+// current buffers on the context's stream, then frac_set_planes' path (planes_changed).  Every argument is
+// checked before anything is touched.
+int frac_set_planes_device(frac_ctx* c, const void* d_src, uint32_t sw, uint32_t sh, uint32_t sstride,
+                           const void* d_tgt, uint32_t tw, uint32_t th, uint32_t tstride)
+{
+    if (!c)
+        return FRAC_E_INVALID;
+    if (!d_src || sw == 0 || sh == 0 || sstride < sw)
+        return c->fail(FRAC_E_INVALID, "invalid device source plane");
+    const bool same = d_tgt == nullptr || d_tgt == d_src;
+    if (same)
+        return set_frame_device(c, d_src, sw, sh, sstride, true);
+    if (tw == 0 || th == 0 || tstride < tw)
+        return c->fail(FRAC_E_INVALID, "invalid device target plane");
+    FRAC_HIP(c, hipSetDevice(c->device));
+    FRAC_TRY(settle_fallback(c)); // the last run's fp32-regime ranges read the planes these copies overwrite
+    const uint32_t sp = plane_pitch(sw), tp = plane_pitch(tw);
+    FRAC_HIP(c, c->d_src.ensure((size_t)sp * (sh + 1)));
+    FRAC_HIP(c, c->d_tgt.ensure((size_t)tp * (th + 1)));
+    c->d_sstride = sp;
+    c->d_tstride = tp;
+    FRAC_TRY(copy_plane(c, c->d_src.ptr, sp, d_src, sstride, sw, sh, hipMemcpyDeviceToDevice, c->stream));
+    FRAC_TRY(copy_plane(c, c->d_tgt.ptr, tp, d_tgt, tstride, tw, th, hipMemcpyDeviceToDevice, c->stream));
+    FRAC_HIP(c, hipStreamSynchronize(c->stream));
+    planes_changed(c, sw, sh, tw, th, false);
+    return FRAC_OK;
 }
 
 // Frame streaming from host memory (frac_ctx::FrameStream has the ordering)

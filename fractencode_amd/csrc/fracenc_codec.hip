@@ -1,5 +1,6 @@
-// fracenc_codec.hip — the decoders (items, a run's results, FRC1 / FRQ1 streams, FRC3 colour containers), the
-// stream packers and parsers, and the colour conversion entry points.  Included by fracenc_api.hip.
+// fracenc_codec.hip — the decoders (items, a run's results, FRC1 / FRQ1 streams iteratively or once against a
+// reference plane, FRC3 colour containers), the stream packers and parsers, and the colour conversion entry points.
+// Included by fracenc_api.hip.
 extern "C" {
 
 int frac_rgb_to_yuv_device(frac_ctx* c, const void* d_rgb, uint32_t w, uint32_t h, uint32_t rgb_stride, void* d_y,
@@ -561,14 +562,22 @@ int frac_frc1_info(const uint8_t* stream, size_t len, struct frac_frc1_info* out
     return rc;
 }
 
-// frac_decode_frc1 past its argument checks: the parsed stream `h` (records at stream + 72) decoded at `scale`
-// (checked by the caller) from and to `io`.
-static int decode_frc1_parsed(frac_ctx* c, const Frc1Info& h, const uint8_t* stream, uint32_t scale, int max_iter,
-                              double rms_eps, const PlaneIO& io, int* iterations, double* rms)
-{
-    const uint32_t W = scale * h.width, H = scale * h.height;
-    const uint32_t n = h.n_ranges;
+// A parsed FRC1 stream's records on the device, validated: what the iterative and the inter decoders share.
+struct Frc1Device {
     Frc1Layout L{};
+    uint32_t n = 0;     // records, in d_frc_rec
+    bool tiles = false; // the ranges tile the frame and every range has a domain
+    bool fast = false;  // the step kernels' geometry: tiles, domain side twice the range side, no stepwise flag
+};
+
+// The record pass of the parsed stream `h` (records at stream + 72): the layout by value, the records unpacked
+// into d_frc_rec and their indices checked.  Blocks for the status word; FRAC_E_INVALID for an index above the
+// domain count, before anything else has been launched.
+static int frc1_records_device(frac_ctx* c, const Frc1Info& h, const uint8_t* stream, Frc1Device* d)
+{
+    const uint32_t n = h.n_ranges;
+    Frc1Layout& L = d->L;
+    L = Frc1Layout{};
     L.n_ranges = n;
     L.n_domains = h.n_domains;
     L.rcols = n ? (h.width - h.range_size) / h.range_size + 1 : 0;
@@ -612,15 +621,38 @@ static int decode_frc1_parsed(frac_ctx* c, const Frc1Info& h, const uint8_t* str
         if (status[0])
             return c->fail(FRAC_E_INVALID, "FRC1: domain index out of range");
     }
-    const bool tiles = n && h.width % h.range_size == 0 && h.height % h.range_size == 0 && status[1] == 0;
-    if (tiles && h.domain_size == 2 * h.range_size && !(c->p.flags & FRAC_FLAG_DECODE_STEPWISE)) {
-        Frc1StepArgs a;
-        a.w = W;
-        a.h = H;
-        a.R = scale * h.range_size;
-        a.rrows = h.height / h.range_size;
-        a.scale = scale;
-        a.rec = c->d_frc_rec.ptr;
+    d->n = n;
+    d->tiles = n && h.width % h.range_size == 0 && h.height % h.range_size == 0 && status[1] == 0;
+    d->fast = d->tiles && h.domain_size == 2 * h.range_size && !(c->p.flags & FRAC_FLAG_DECODE_STEPWISE);
+    return FRAC_OK;
+}
+
+// the step kernels' arguments of a stream on their geometry at `scale`, but for the planes
+static Frc1StepArgs frc1_step_args(frac_ctx* c, const Frc1Info& h, uint32_t scale)
+{
+    Frc1StepArgs a{};
+    a.w = scale * h.width;
+    a.h = scale * h.height;
+    a.R = scale * h.range_size;
+    a.rrows = h.height / h.range_size;
+    a.scale = scale;
+    a.rec = c->d_frc_rec.ptr;
+    return a;
+}
+
+// frac_decode_frc1 past its argument checks: the parsed stream `h` (records at stream + 72) decoded at `scale`
+// (checked by the caller) from and to `io`.
+static int decode_frc1_parsed(frac_ctx* c, const Frc1Info& h, const uint8_t* stream, uint32_t scale, int max_iter,
+                              double rms_eps, const PlaneIO& io, int* iterations, double* rms)
+{
+    const uint32_t W = scale * h.width, H = scale * h.height;
+    Frc1Device d;
+    FRAC_TRY(frc1_records_device(c, h, stream, &d));
+    const Frc1Layout& L = d.L;
+    const uint32_t n = d.n;
+    const bool tiles = d.tiles;
+    if (d.fast) {
+        Frc1StepArgs a = frc1_step_args(c, h, scale);
         const dim3 grid((W + kFrc1TileW - 1) / kFrc1TileW, (H + kFrc1TileH - 1) / kFrc1TileH);
         return decode_fused_loop(c, W, H, max_iter < 0 ? 300 : max_iter, rms_eps, io, iterations, rms,
                                  [&](const uint8_t* src, uint8_t* tgt, uint32_t stride) {
@@ -920,14 +952,23 @@ static int frq1_decodable(frac_ctx* c, const Frq1Info& h)
     return FRAC_OK;
 }
 
-// frac_decode_frq1 past its argument checks: the parsed stream `h` (body at stream + 64) decoded at `scale`
-// (checked by the caller) from and to `io`.
-static int decode_frq1_parsed(frac_ctx* c, const Frq1Info& h, const uint8_t* stream, uint32_t scale, int max_iter,
-                              double rms_eps, const PlaneIO& io, int* iterations, double* rms)
-{
-    const uint32_t W = scale * h.width, H = scale * h.height;
-    const uint32_t n = h.n_leaves;
+// A parsed FRQ1 stream's leaves on the device, validated: what the iterative and the inter decoders share.
+struct Frq1Device {
     Frq1Layout L{};
+    uint32_t n = 0;     // leaves, in d_frq_leaves
+    uint32_t mcols = 0; // the cell map's columns (d_frq_map, filled when the level-0 grid covers the frame)
+    bool whole = false; // the leaves tile the frame and every leaf has a domain
+    bool fast = false;  // the step kernels' geometry: whole, no stepwise flag
+};
+
+// The layout pass of the parsed stream `h` (body at stream + 64): the layout by value, the leaf entries in
+// d_frq_leaves, the cell map and the indices checked.  Blocks for the status word; FRAC_E_INVALID for an index
+// above its level's domain count, before anything else has been launched.
+static int frq1_layout_device(frac_ctx* c, const Frq1Info& h, const uint8_t* stream, Frq1Device* d)
+{
+    const uint32_t n = h.n_leaves;
+    Frq1Layout& L = d->L;
+    L = Frq1Layout{};
     L.n_leaves = n;
     L.dc1 = L.dc2 = L.dc3 = L.dc4 = 1;
     for (uint32_t k = 0; k < h.levels; ++k) {
@@ -1019,16 +1060,40 @@ static int decode_frq1_parsed(frac_ctx* c, const Frq1Info& h, const uint8_t* str
         if (status[0])
             return c->fail(FRAC_E_INVALID, "FRQ1: domain index out of range");
     }
-    const bool whole = tiles && status[1] == 0; // every pixel written by a leaf with a domain
-    if (whole && !(c->p.flags & FRAC_FLAG_DECODE_STEPWISE)) {
-        Frq1StepArgs a;
-        a.w = W;
-        a.h = H;
-        a.scale = scale;
-        a.cell = h.min_size * scale;
-        a.mcols = mcols;
-        a.map = c->d_frq_map.ptr;
-        a.leaves = c->d_frq_leaves.ptr;
+    d->n = n;
+    d->mcols = mcols;
+    d->whole = tiles && status[1] == 0; // every pixel written by a leaf with a domain
+    d->fast = d->whole && !(c->p.flags & FRAC_FLAG_DECODE_STEPWISE);
+    return FRAC_OK;
+}
+
+// the step kernels' arguments of a stream on their geometry at `scale`, but for the planes
+static Frq1StepArgs frq1_step_args(frac_ctx* c, const Frq1Info& h, const Frq1Device& d, uint32_t scale)
+{
+    Frq1StepArgs a{};
+    a.w = scale * h.width;
+    a.h = scale * h.height;
+    a.scale = scale;
+    a.cell = h.min_size * scale;
+    a.mcols = d.mcols;
+    a.map = c->d_frq_map.ptr;
+    a.leaves = c->d_frq_leaves.ptr;
+    return a;
+}
+
+// frac_decode_frq1 past its argument checks: the parsed stream `h` (body at stream + 64) decoded at `scale`
+// (checked by the caller) from and to `io`.
+static int decode_frq1_parsed(frac_ctx* c, const Frq1Info& h, const uint8_t* stream, uint32_t scale, int max_iter,
+                              double rms_eps, const PlaneIO& io, int* iterations, double* rms)
+{
+    const uint32_t W = scale * h.width, H = scale * h.height;
+    Frq1Device d;
+    FRAC_TRY(frq1_layout_device(c, h, stream, &d));
+    const Frq1Layout& L = d.L;
+    const uint32_t n = d.n;
+    const bool whole = d.whole;
+    if (d.fast) {
+        Frq1StepArgs a = frq1_step_args(c, h, d, scale);
         const dim3 grid((W + kFrc1TileW - 1) / kFrc1TileW, (H + kFrc1TileH - 1) / kFrc1TileH);
         return decode_fused_loop(c, W, H, max_iter < 0 ? 300 : max_iter, rms_eps, io, iterations, rms,
                                  [&](const uint8_t* src, uint8_t* tgt, uint32_t stride) {
@@ -1067,6 +1132,183 @@ int frac_decode_frq1(frac_ctx* c, const uint8_t* stream, size_t len, uint32_t sc
         return c->fail(FRAC_E_INVALID, "decode_frq1: the plane is smaller than the scaled frame");
     FRAC_TRY(frq1_decodable(c, h));
     return decode_frq1_parsed(c, h, stream, scale, max_iter, rms_eps, host_plane(plane), iterations, rms);
+}
+
+// ---- inter-coded frames: a stream applied once to a reference plane (fracenc_inter.hip) -----------
+
+} // extern "C"
+
+// An FRC1 or FRQ1 stream opened for an inter pass: told apart by its magic, parsed and checked as the iterative
+// decoders check it; after inter_records also its records or leaves on the device.
+struct InterStream {
+    bool quad = false;
+    Frc1Info h1{};
+    Frq1Info hq{};
+    Frc1Device d1;
+    Frq1Device dq;
+    uint32_t width() const { return quad ? hq.width : h1.width; }
+    uint32_t height() const { return quad ? hq.height : h1.height; }
+    uint32_t grid() const { return quad ? hq.max_size : h1.range_size; } // the covered rectangle's g
+    uint32_t items() const { return quad ? dq.n : d1.n; }
+    bool fast() const { return quad ? dq.fast : d1.fast; }
+};
+
+// everything an inter pass refuses by the stream and the scale, before any launch
+static int inter_open(frac_ctx* c, const char* what, const uint8_t* stream, size_t len, uint32_t scale, InterStream* s)
+{
+    s->quad = stream && len >= 4 && std::memcmp(stream, "FRQ1", 4) == 0;
+    {
+        std::string msg;
+        if (!s->quad && !(stream && len >= 4 && std::memcmp(stream, "FRC1", 4) == 0))
+            return c->fail(FRAC_E_INVALID, std::string(what) + ": neither an FRC1 nor an FRQ1 stream");
+        if ((s->quad ? frq1_parse(stream, len, &s->hq, msg) : frc1_parse(stream, len, &s->h1, msg)) != FRAC_OK)
+            return c->fail(FRAC_E_INVALID, msg);
+    }
+    FRAC_TRY(check_ab_knobs(c));
+    if (scale < 1 || scale > 16 || (uint64_t)scale * s->width() > 65535 || (uint64_t)scale * s->height() > 65535)
+        return c->fail(FRAC_E_INVALID,
+                       std::string(what) + ": scale must be in 1..16 and the scaled frame at most 65535 a side");
+    if (s->quad)
+        FRAC_TRY(frq1_decodable(c, s->hq));
+    return FRAC_OK;
+}
+
+// the record or layout pass of an opened stream; blocks for its status word
+static int inter_records(frac_ctx* c, const uint8_t* stream, InterStream* s)
+{
+    return s->quad ? frq1_layout_device(c, s->hq, stream, &s->dq) : frc1_records_device(c, s->h1, stream, &s->d1);
+}
+
+// a plane whose taps the fast kernels address modulo 2^32: its byte span must not exceed 2^32
+static bool inter_span_ok(uint32_t pitch, uint32_t w, uint32_t h)
+{
+    return (uint64_t)pitch * (h - 1) + w <= (1ull << 32);
+}
+
+// The fast route of a stream for which s.fast() holds, enqueued on the context's stream: taps from `ref`
+// (inter_span_ok), the result stored and / or compared as `io` says.
+template <bool kWrite, bool kSse>
+static int inter_launch_fast(frac_ctx* c, const InterStream& s, uint32_t scale, const uint8_t* ref, uint32_t rpitch,
+                             const InterOut& io)
+{
+    const uint32_t W = scale * s.width(), H = scale * s.height();
+    const dim3 grid((W + kFrc1TileW - 1) / kFrc1TileW, (H + kFrc1TileH - 1) / kFrc1TileH);
+    if (s.quad) {
+        Frq1StepArgs a = frq1_step_args(c, s.hq, s.dq, scale);
+        a.src = ref;
+        a.stride = rpitch;
+        inter_frq1<kWrite, kSse><<<grid, 256, 0, c->stream>>>(a, s.dq.L, io);
+    } else {
+        Frc1StepArgs a = frc1_step_args(c, s.h1, scale);
+        a.src = ref;
+        a.stride = rpitch;
+        inter_frc1<kWrite, kSse><<<grid, 256, 0, c->stream>>>(a, s.d1.L, io);
+    }
+    FRAC_HIP(c, hipGetLastError());
+    return FRAC_OK;
+}
+
+// The general route, enqueued on the context's stream: `dst` filled from `ref` (row by row: the bytes between the
+// destination's rows are not ours), the records or leaves expanded into scaled items, one inter_apply over them.
+static int inter_launch_general(frac_ctx* c, const InterStream& s, uint32_t scale, const uint8_t* ref, uint32_t rpitch,
+                                uint8_t* dst, uint32_t dpitch)
+{
+    const uint32_t W = scale * s.width(), H = scale * s.height(), n = s.items();
+    if (rpitch == W && dpitch == W)
+        FRAC_HIP(c, hipMemcpyAsync(dst, ref, (size_t)W * H, hipMemcpyDeviceToDevice, c->stream));
+    else
+        FRAC_HIP(c, hipMemcpy2DAsync(dst, dpitch, ref, rpitch, W, H, hipMemcpyDeviceToDevice, c->stream));
+    if (!n)
+        return FRAC_OK;
+    FRAC_HIP(c, c->d_dec_items.ensure(n));
+    if (s.quad)
+        frq1dec_expand<<<(n + 255) / 256, 256, 0, c->stream>>>(c->d_frq_leaves.ptr, s.dq.L, scale, c->d_dec_items.ptr);
+    else
+        frc1dec_expand<<<(n + 255) / 256, 256, 0, c->stream>>>(c->d_frc_rec.ptr, s.d1.L, scale, c->d_dec_items.ptr);
+    InterApplyArgs a;
+    a.ref = ref;
+    a.dst = dst;
+    a.rpitch = rpitch;
+    a.dpitch = dpitch;
+    a.items = c->d_dec_items.ptr;
+    a.n = n;
+    inter_apply<<<(n + 3) / 4, 256, 0, c->stream>>>(a);
+    FRAC_HIP(c, hipGetLastError());
+    return FRAC_OK;
+}
+
+// Both entry points.  Host planes (h_ref, h_plane; tight rows) are staged in the decoder's buffers and the call
+// returns synchronised; device planes are read and written in place on the context's stream.
+static int decode_inter_impl(frac_ctx* c, const uint8_t* stream, size_t len, uint32_t scale, const uint8_t* h_ref,
+                             uint8_t* h_plane, const void* d_ref, uint32_t ref_stride, void* d_plane,
+                             uint32_t plane_stride, size_t plane_bytes)
+{
+    if (!c)
+        return FRAC_E_INVALID;
+    InterStream s;
+    FRAC_TRY(inter_open(c, "decode_inter", stream, len, scale, &s));
+    const uint32_t W = scale * s.width(), H = scale * s.height();
+    const bool host = h_ref || h_plane;
+    if (host ? (!h_ref || !h_plane) : (!d_ref || !d_plane))
+        return c->fail(FRAC_E_INVALID, "decode_inter: ref or plane is NULL");
+    if (host)
+        ref_stride = plane_stride = W;
+    if (ref_stride < W || plane_stride < W)
+        return c->fail(FRAC_E_INVALID, "decode_inter: a stride below the scaled frame's width");
+    const uint64_t rspan = (uint64_t)ref_stride * (H - 1) + W, pspan = (uint64_t)plane_stride * (H - 1) + W;
+    if (plane_bytes < pspan)
+        return c->fail(FRAC_E_INVALID, "decode_inter: plane_bytes is short of the scaled frame's last row");
+    if (!host) {
+        if (!inter_span_ok(ref_stride, W, H))
+            return c->fail(FRAC_E_INVALID, "decode_inter: the reference plane spans more than 2^32 bytes");
+        const uintptr_t r0 = reinterpret_cast<uintptr_t>(d_ref), p0 = reinterpret_cast<uintptr_t>(d_plane);
+        if (r0 < p0 + pspan && p0 < r0 + rspan)
+            return c->fail(FRAC_E_INVALID, "decode_inter: ref and plane overlap (an apply in place would read what it "
+                                           "wrote)");
+    }
+    FRAC_TRY(inter_records(c, stream, &s)); // refuses a bad index before any byte of a plane is written
+    const uint8_t* ref = static_cast<const uint8_t*>(d_ref);
+    uint8_t* dst = static_cast<uint8_t*>(d_plane);
+    if (host) {
+        const uint32_t pitch = plane_pitch(W);
+        const size_t bytes = (size_t)pitch * (H + 1);
+        FRAC_HIP(c, c->d_dec_src.ensure(bytes));
+        FRAC_HIP(c, c->d_dec_tgt.ensure(bytes));
+        FRAC_HIP(c, hipMemcpy2DAsync(c->d_dec_src.ptr, pitch, h_ref, W, W, H, hipMemcpyHostToDevice, c->stream));
+        ref = c->d_dec_src.ptr, dst = c->d_dec_tgt.ptr;
+        ref_stride = plane_stride = pitch;
+    }
+    if (s.fast()) {
+        InterOut io{};
+        io.dst = dst;
+        io.dpitch = plane_stride;
+        io.dwords = (reinterpret_cast<uintptr_t>(dst) | plane_stride) % 4 == 0;
+        FRAC_TRY((inter_launch_fast<true, false>(c, s, scale, ref, ref_stride, io)));
+    } else {
+        FRAC_TRY(inter_launch_general(c, s, scale, ref, ref_stride, dst, plane_stride));
+    }
+    if (host) {
+        FRAC_HIP(c, hipMemcpy2DAsync(h_plane, W, dst, plane_stride, W, H, hipMemcpyDeviceToHost, c->stream));
+        FRAC_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    return FRAC_OK;
+}
+
+extern "C" {
+
+int frac_decode_inter(frac_ctx* c, const uint8_t* stream, size_t len, uint32_t scale, const uint8_t* ref,
+                      uint8_t* plane, size_t plane_bytes)
+{
+    if (c && (!ref || !plane))
+        return c->fail(FRAC_E_INVALID, "decode_inter: ref or plane is NULL");
+    return decode_inter_impl(c, stream, len, scale, ref, plane, nullptr, 0, nullptr, 0, plane_bytes);
+}
+
+int frac_decode_inter_device(frac_ctx* c, const uint8_t* stream, size_t len, uint32_t scale, const void* d_ref,
+                             uint32_t ref_stride, void* d_plane, uint32_t plane_stride, size_t plane_bytes)
+{
+    return decode_inter_impl(c, stream, len, scale, nullptr, nullptr, d_ref, ref_stride, d_plane, plane_stride,
+                             plane_bytes);
 }
 
 // ---- FRC3: the colour container (fractencode_amd/codec.py documents the layout) -------------------

@@ -137,7 +137,7 @@ __device__ inline uint32_t frc1_step_y(uint32_t t, uint32_t stride)
 struct Frc1StepArgs {
     const uint8_t* src;
     uint8_t* tgt;
-    uint32_t stride;            // plane row stride, a multiple of 64
+    uint32_t stride;            // plane row stride, a multiple of 64 (inter_frc1: the reference's pitch, any value)
     uint32_t w, h;              // scaled plane: rcols·R × rrows·R
     uint32_t R;                 // scaled range side; the domain patch is 2R square
     uint32_t rrows;             // range grid rows

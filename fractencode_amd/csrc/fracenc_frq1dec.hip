@@ -155,7 +155,7 @@ constexpr uint32_t kFrq1Org = frq1_org_codes();
 struct Frq1StepArgs {
     const uint8_t* src;
     uint8_t* tgt;
-    uint32_t stride; // plane row stride, a multiple of 64
+    uint32_t stride; // plane row stride, a multiple of 64 (inter_frq1: the reference's pitch, any value)
     uint32_t w, h;   // scaled plane
     uint32_t scale;
     uint32_t cell;   // scaled side of a map cell: min_size · scale

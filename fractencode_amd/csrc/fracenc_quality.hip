@@ -42,6 +42,10 @@
 //   (and _device)               (frc3_open, frc3_decode_planes), yuv_rgb_sse against the caller's RGB over the
 //                               rectangle all three planes' grids cover; the host variant's RGB is uploaded behind
 //                               the planes in d_frc3, rows as far apart as the caller's
+//   frac_inter_error            the stream opened as frac_decode_inter opens it and applied once, at scale 1, to
+//                               the plane the domains lie on: on the fast route inter_frc1 / inter_frq1 compare
+//                               in registers with the plane the ranges lie on and write nothing; every other
+//                               stream is applied into the decoder's target buffer and compared by plane_sse_blocks
 // The decoded plane, the frame and the leaves never cross PCIe.
 
 namespace {
@@ -234,6 +238,46 @@ int yuv_rgb_sse_launch(frac_ctx* c, const YuvSseArgs& a)
     return FRAC_OK;
 }
 
+// Σ(plane − frame)² over the bw × bh blocks (at least one) of g × g pixels from the origin, with the plane the
+// ranges lie on as the frame; `plane` is device memory, read on the context's stream.  block_sse (host memory, or
+// NULL) gets nb block sums.  Returns synchronised.
+int frame_sse_of(frac_ctx* c, const uint8_t* plane, uint32_t pitch, uint32_t bw, uint32_t bh, uint32_t g,
+                 uint64_t* block_sse, size_t nb, uint64_t* sse)
+{
+    auto& Q = c->quality;
+    const uint64_t blocks = (uint64_t)bw * bh;
+    FRAC_HIP(c, Q.d_total.ensure(1));
+    FRAC_HIP(c, Q.h_total.ensure());
+    if (nb)
+        FRAC_HIP(c, Q.d_block.ensure(nb));
+    FRAC_HIP(c, hipMemsetAsync(Q.d_total.ptr, 0, sizeof(unsigned long long), c->stream));
+    const PlaneRef frame = target_plane(c);
+    PlaneSseArgs a{};
+    a.a = plane, a.pitch_a = pitch;
+    a.b = frame.ptr, a.pitch_b = frame.stride;
+    a.bw = bw, a.bh = bh, a.g = g;
+    a.dwords = g % 4 == 0 && pitch % 4 == 0 && frame.stride % 4 == 0 &&
+               (reinterpret_cast<uintptr_t>(plane) | reinterpret_cast<uintptr_t>(frame.ptr)) % 4 == 0;
+    const uint64_t units = a.dwords ? (uint64_t)(g / 4) * g : (uint64_t)g * g;
+    while (a.lanes_lg < 6 && (1ull << a.lanes_lg) < units)
+        ++a.lanes_lg;
+    a.block_sse = nb ? Q.d_block.ptr : nullptr;
+    a.block_cap = nb;
+    a.total = Q.d_total.ptr;
+    const uint64_t per_wg = 4ull * (64u >> a.lanes_lg);
+    const uint32_t wgs = (uint32_t)std::min<uint64_t>((blocks + per_wg - 1) / per_wg, 8192);
+    plane_sse_blocks<<<wgs, 256, 0, c->stream>>>(a);
+    FRAC_HIP(c, hipGetLastError());
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long));
+    FRAC_HIP(c, hipMemcpyAsync(Q.h_total.ptr, Q.d_total.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                               c->stream));
+    if (nb)
+        FRAC_HIP(c, hipMemcpyAsync(block_sse, Q.d_block.ptr, nb * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    FRAC_HIP(c, hipStreamSynchronize(c->stream));
+    *sse = *Q.h_total.ptr;
+    return FRAC_OK;
+}
+
 // what one stream's decode and comparison give
 struct StreamError {
     uint64_t sse = 0, pixels = 0, blocks = 0;
@@ -287,38 +331,62 @@ int decode_error_of(frac_ctx* c, const uint8_t* stream, size_t len, int max_iter
         FRAC_HIP(c, hipStreamSynchronize(c->stream));
         return FRAC_OK;
     }
-    auto& Q = c->quality;
     const size_t nb = block_sse ? (size_t)std::min<uint64_t>(r->blocks, block_cap) : 0;
-    FRAC_HIP(c, Q.d_total.ensure(1));
-    FRAC_HIP(c, Q.h_total.ensure());
-    if (nb)
-        FRAC_HIP(c, Q.d_block.ensure(nb));
-    FRAC_HIP(c, hipMemsetAsync(Q.d_total.ptr, 0, sizeof(unsigned long long), c->stream));
+    return frame_sse_of(c, fin.ptr, fin.pitch, bw, bh, g, block_sse, nb, &r->sse);
+}
+
+// what an inter pass and its comparison give
+struct InterError {
+    uint64_t sse = 0, pixels = 0;
+};
+
+// The stream applied at scale 1 to the plane the domains lie on and compared with the plane the ranges lie on,
+// over the covered rectangle; returns synchronised.  On the fast route the sums come from the kernel's registers
+// and no plane is written; every other stream is applied into the decoder's target buffer and compared there.
+int inter_error_of(frac_ctx* c, const uint8_t* stream, size_t len, InterError* r)
+{
+    *r = InterError{};
+    InterStream s;
+    FRAC_TRY(inter_open(c, "inter_error", stream, len, 1, &s));
+    if (!c->planes_set)
+        return c->fail(FRAC_E_STATE, "inter_error: no planes set");
+    const uint32_t W = s.width(), H = s.height(), g = s.grid();
+    const frac_ctx::PlaneSize& fr = c->same_plane ? c->src : c->tgt;
+    if (W != c->src.w || H != c->src.h || W != fr.w || H != fr.h)
+        return c->fail(FRAC_E_INVALID, "inter_error: the stream's frame is " + std::to_string(W) + "x" +
+                                           std::to_string(H) + ", the planes set are " + std::to_string(c->src.w) +
+                                           "x" + std::to_string(c->src.h) + " and " + std::to_string(fr.w) + "x" +
+                                           std::to_string(fr.h));
+    if (g == 0)
+        return c->fail(FRAC_E_INVALID, "inter_error: a range size of zero");
+    FRAC_TRY(inter_records(c, stream, &s));
+    const uint32_t bw = W / g, bh = H / g;
+    r->pixels = (uint64_t)bw * bh * g * g;
+    if (!r->pixels) {
+        FRAC_HIP(c, hipStreamSynchronize(c->stream));
+        return FRAC_OK;
+    }
     const PlaneRef frame = target_plane(c);
-    PlaneSseArgs a{};
-    a.a = fin.ptr, a.pitch_a = fin.pitch;
-    a.b = frame.ptr, a.pitch_b = frame.stride;
-    a.bw = bw, a.bh = bh, a.g = g;
-    a.dwords = g % 4 == 0 && fin.pitch % 4 == 0 && frame.stride % 4 == 0 &&
-               (reinterpret_cast<uintptr_t>(fin.ptr) | reinterpret_cast<uintptr_t>(frame.ptr)) % 4 == 0;
-    const uint64_t units = a.dwords ? (uint64_t)(g / 4) * g : (uint64_t)g * g;
-    while (a.lanes_lg < 6 && (1ull << a.lanes_lg) < units)
-        ++a.lanes_lg;
-    a.block_sse = nb ? Q.d_block.ptr : nullptr;
-    a.block_cap = nb;
-    a.total = Q.d_total.ptr;
-    const uint64_t per_wg = 4ull * (64u >> a.lanes_lg);
-    const uint32_t wgs = (uint32_t)std::min<uint64_t>((r->blocks + per_wg - 1) / per_wg, 8192);
-    plane_sse_blocks<<<wgs, 256, 0, c->stream>>>(a);
-    FRAC_HIP(c, hipGetLastError());
-    static_assert(sizeof(uint64_t) == sizeof(unsigned long long));
-    FRAC_HIP(c, hipMemcpyAsync(Q.h_total.ptr, Q.d_total.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                               c->stream));
-    if (nb)
-        FRAC_HIP(c, hipMemcpyAsync(block_sse, Q.d_block.ptr, nb * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    FRAC_HIP(c, hipStreamSynchronize(c->stream));
-    r->sse = *Q.h_total.ptr;
-    return FRAC_OK;
+    auto& Q = c->quality;
+    if (s.fast()) { // the ranges tile the frame: the covered rectangle is the frame
+        FRAC_HIP(c, Q.d_total.ensure(1));
+        FRAC_HIP(c, Q.h_total.ensure());
+        FRAC_HIP(c, hipMemsetAsync(Q.d_total.ptr, 0, sizeof(unsigned long long), c->stream));
+        InterOut io{};
+        io.frame = frame.ptr;
+        io.fpitch = frame.stride;
+        io.total = Q.d_total.ptr;
+        FRAC_TRY((inter_launch_fast<false, true>(c, s, 1, c->d_src.ptr, c->d_sstride, io)));
+        FRAC_HIP(c, hipMemcpyAsync(Q.h_total.ptr, Q.d_total.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                   c->stream));
+        FRAC_HIP(c, hipStreamSynchronize(c->stream));
+        r->sse = *Q.h_total.ptr;
+        return FRAC_OK;
+    }
+    const uint32_t pitch = plane_pitch(W);
+    FRAC_HIP(c, c->d_dec_tgt.ensure((size_t)pitch * (H + 1)));
+    FRAC_TRY(inter_launch_general(c, s, 1, c->d_src.ptr, c->d_sstride, c->d_dec_tgt.ptr, pitch));
+    return frame_sse_of(c, c->d_dec_tgt.ptr, pitch, bw, bh, g, nullptr, 0, &r->sse);
 }
 
 // One probe of the rate readers: the rate state's stream at `split`, packed as frac_quadtree_rate_stream packs
@@ -504,6 +572,19 @@ int frac_decode_error(frac_ctx* c, const uint8_t* stream, size_t len, int max_it
         *iterations = r.iterations;
     if (rms)
         *rms = r.rms;
+    return FRAC_OK;
+}
+
+int frac_inter_error(frac_ctx* c, const uint8_t* stream, size_t len, uint64_t* sse, uint64_t* pixels)
+{
+    if (!c)
+        return FRAC_E_INVALID;
+    InterError r;
+    FRAC_TRY(inter_error_of(c, stream, len, &r));
+    if (sse)
+        *sse = r.sse;
+    if (pixels)
+        *pixels = r.pixels;
     return FRAC_OK;
 }
 

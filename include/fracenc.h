@@ -705,6 +705,65 @@ int frac_decode_error_frc3_device(frac_ctx* ctx, const uint8_t* stream, size_t l
                                   uint64_t* pixels, int iterations[3], double rms[3]);
 int frac_quadtree_rate_candidates(frac_ctx* ctx, double* out, size_t cap, size_t* n_out);
 
+/* ---- inter-coded frames: a stream decoded against a reference plane ----
+ * These four symbols were added after ABI 9 without changing FRAC_ABI_VERSION: probe for them by name
+ * (dlsym) when the library may be older.
+ *
+ * A search over two planes (frac_set_planes: domains on the source plane, ranges on the target plane) gives
+ * records that mean "range = s·(domain of the other plane) + o".  Packed, they are ordinary FRC1 / FRQ1 bytes: a
+ * record carries no source plane, as it carries no resolution, and no header flag says how a stream is to be
+ * decoded.  That is the caller's choice of call: the iterative decoders take a stream to its fixed point on one
+ * plane, frac_decode_inter applies it once to a reference plane.  One application needs no convergence test and
+ * puts no contractivity condition on the contrast; with the decoder's own previous output as the reference a
+ * sequence is coded closed-loop, without drift.
+ *
+ * frac_decode_inter / frac_decode_inter_device: `stream` is an FRC1 or an FRQ1 stream, told apart by its magic,
+ * parsed and validated exactly as frac_decode_frc1 / frac_decode_frq1 do; `scale` as there (1..16, the scaled
+ * frame at most 65535 a side).  `ref` and `plane` are each (scale·W) × (scale·H).  The result, which is the
+ * definition: `plane` is a copy of `ref`; then, for every record or leaf that has a domain, one Frac::copy —
+ * clamp(trunc(fma(s, sample/4, o))) with the sampler's 2×2 integer sum and the dequantized s and o, the iterative
+ * decoders' arithmetic — reads the domain patch in `ref` and writes the range in `plane`, every coordinate and
+ * size multiplied by `scale`.  Pixels that no such range covers (margins, records whose index is the domain
+ * count) keep the reference's value.  Ranges do not overlap, so the order does not matter.  There is one pass:
+ * no iterations or rms outputs.
+ * The host variant takes tight planes (row stride scale·W), stages them in buffers of the context and returns
+ * synchronised.  In the device variant the planes are read and written in place, every stride is in bytes and at
+ * least scale·W, and plane_bytes covers the last row (plane_stride·(scale·H − 1) + scale·W); no byte between
+ * the rows of d_plane or after its last row is written.  The call is ordered on the ctx stream; it may block for
+ * the record pass's status word, as frac_decode_frc1 does, and does not wait for the pixel pass.
+ * FRAC_E_INVALID, with no byte of `plane` written: everything the iterative decoders refuse (a record index above
+ * its domain count included: the record or layout pass finds it before any plane write); a NULL ref or plane; a
+ * stride below scale·W; plane_bytes too small; device ref and plane whose byte spans overlap (an apply in place
+ * would read what it wrote; a plane's span runs from its first byte to its last row's end, stride·(scale·H − 1) +
+ * scale·W bytes, the bytes between its rows included: two strided views that interleave in one buffer, such as its
+ * left and right halves, are refused although they share no pixel); a device reference plane whose span exceeds
+ * 2^32 bytes (the pixel pass addresses the reference with 32-bit offsets).
+ * The calls are readers, like frac_decode_error: a run's readable results, the rate state and the tuple sink stay
+ * as they were, no frame needs to be set, only the decoder's buffers are touched.
+ *
+ * frac_inter_error: the stream applied at scale 1 to the context's source plane (the plane the domains lie on) and
+ * compared with the plane the ranges lie on: the target plane of frac_set_planes, or the same plane after
+ * frac_set_frame — the exact post-quantization error of a two-plane stream, or the quantized collage error of an
+ * ordinary one.  The covered rectangle and *pixels are frac_decode_error's: (W − W % g) × (H − H % g) with g the
+ * FRC1 range_size or the FRQ1 max_size; *sse is the exact unsigned 64-bit Σ(applied − frame)² over it; pixels
+ * left at the reference's value are counted like any other.  FRAC_E_STATE without planes; FRAC_E_INVALID when the
+ * stream's frame is not both planes' size, and for every stream frac_decode_inter refuses.  Returns synchronised;
+ * a reader, ordered behind a pending frac_set_frame_async copy as frac_decode_error is.  Either output may be
+ * NULL.  Where the ranges or leaves tile the frame, each with a domain of twice its side, no plane is written:
+ * the pass compares in registers.
+ *
+ * frac_set_planes_device: frac_set_planes with both planes already in device memory (strides in bytes), copied
+ * device to device as frac_set_frame_device copies one; d_tgt NULL or equal to d_src is frac_set_frame_device.  A
+ * setter: it ends the last run's results and the rate state; a failed argument check changes nothing.  It blocks
+ * until the copies are done. */
+int frac_decode_inter(frac_ctx* ctx, const uint8_t* stream, size_t len, uint32_t scale, const uint8_t* ref,
+                      uint8_t* plane, size_t plane_bytes);
+int frac_decode_inter_device(frac_ctx* ctx, const uint8_t* stream, size_t len, uint32_t scale, const void* d_ref,
+                             uint32_t ref_stride, void* d_plane, uint32_t plane_stride, size_t plane_bytes);
+int frac_inter_error(frac_ctx* ctx, const uint8_t* stream, size_t len, uint64_t* sse, uint64_t* pixels);
+int frac_set_planes_device(frac_ctx* ctx, const void* d_src, uint32_t sw, uint32_t sh, uint32_t sstride,
+                           const void* d_tgt, uint32_t tw, uint32_t th, uint32_t tstride);
+
 /* ---- host helpers (no device needed) ------------------------------------ */
 /* createUniformGrid (image/partition2.hpp:109-135): returns the item count and
  * writes min(count, cap) items (categories -1).  Returns 0 where the reference's loop has no

@@ -14,7 +14,8 @@
 //                       computes it (value() with the FMA the compiler contracts)
 //   createUniformGrid / preclassify / encodeQuadtree / decode / decode_frc1 / frc1_info / decode_frq1 / frq1_info /
 //                       pack_frq1 / decode_frc3 / frc3_info / quadtreeRate, rateSizes, rateFit, rateLeaves /
-//                       decodeError, rateErrors, rateQuality — the C ABI entry points
+//                       decodeError, rateErrors, rateQuality / setPlanesDevice, decodeInter, decodeInterDevice,
+//                       interError — the C ABI entry points
 //   Engine's ABI 8/9 methods: an external HIP stream (void*), the tuple sink and 32-byte tuples,
 //                       frame streaming (setFrameAsync / setFrameDeviceAsync), 32-byte quadtree
 //                       leaves, per-run device times
@@ -157,6 +158,15 @@ public:
         check(frac_set_frame_device(ctx_, d_plane, w, h, stride));
         w_ = w;
         h_ = h;
+    }
+    // domains on d_src, ranges on d_tgt, both already on the device, strides in bytes (frac_set_planes_device;
+    // probe for the symbol by name when the library may be older)
+    void setPlanesDevice(const void* d_src, uint32_t sw, uint32_t sh, uint32_t sstride, const void* d_tgt, uint32_t tw,
+                         uint32_t th, uint32_t tstride)
+    {
+        check(frac_set_planes_device(ctx_, d_src, sw, sh, sstride, d_tgt, tw, th, tstride));
+        w_ = sw;
+        h_ = sh;
     }
     // ABI 9: frame streaming.  setFrameAsync uploads on the context's copy stream into its second plane buffer
     // while the runs already enqueued read the current one (pinned host memory makes it asynchronous; the plane
@@ -383,6 +393,37 @@ public:
                                                      r.channel_sse, &r.pixels, r.iterations, r.rms)
                      : frac_decode_error_frc3(ctx_, stream, len, static_cast<const uint8_t*>(rgb), rgb_stride, max_iter,
                                               rms_eps, r.channel_sse, &r.pixels, r.iterations, r.rms));
+        return r;
+    }
+    // Inter-coded frames (include/fracenc.h states the rules): an FRC1 or FRQ1 stream applied once to a reference
+    // plane of scale·W × scale·H.  decodeInter: tight host planes; `plane` is resized and receives the result.
+    // decodeInterDevice: device planes read and written in place on the context's stream, strides in bytes,
+    // plane_bytes up to the last row's end.  interError: the stream applied at scale 1 to the plane the domains
+    // lie on and compared with the plane the ranges lie on, over decodeError's covered rectangle.
+    void decodeInter(const uint8_t* stream, size_t len, const std::vector<uint8_t>& ref, std::vector<uint8_t>& plane,
+                     uint32_t scale = 1)
+    {
+        plane.resize(ref.size());
+        check(frac_decode_inter(ctx_, stream, len, scale, ref.data(), plane.data(), plane.size()));
+    }
+    void decodeInterDevice(const uint8_t* stream, size_t len, const void* d_ref, uint32_t ref_stride, void* d_plane,
+                           uint32_t plane_stride, size_t plane_bytes, uint32_t scale = 1)
+    {
+        check(frac_decode_inter_device(ctx_, stream, len, scale, d_ref, ref_stride, d_plane, plane_stride, plane_bytes));
+    }
+    struct InterError {
+        uint64_t sse, pixels;
+        // 10·log10(255²·pixels / sse); +inf at sse == 0
+        double psnr() const
+        {
+            return sse ? 10.0 * std::log10(255.0 * 255.0 * (double)pixels / (double)sse)
+                       : std::numeric_limits<double>::infinity();
+        }
+    };
+    InterError interError(const uint8_t* stream, size_t len)
+    {
+        InterError r{};
+        check(frac_inter_error(ctx_, stream, len, &r.sse, &r.pixels));
         return r;
     }
     // Decoder2::decode (encode/Encoder2.hpp:67-88); plane holds the caller's initial target
